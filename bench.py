@@ -15,16 +15,25 @@ counts of every ``result.P<NN>`` copied back to host memory.  As in the
 reference's "Server time" (server.lua:464-536), the user finalfn that prints
 results is not part of the step; it runs once after timing to validate.
 
-Before the steady-state steps, ONE cold iteration is timed from the split
-files on disk (page cache dropped with posix_fadvise, best effort) to the
-results in host memory — the shape of the reference's single 49 s run, whose
-mapfns read their split files (examples/WordCount/mapfn.lua:4).  It is
-reported as ``cold_first_iteration_ms`` next to the steady-state headline.
+A plain run sets up, warms up, times the K steps and prints the result line
+(every token counted exactly once is still checked: the count is already on
+the host).  ``--dump-outputs DIR`` also writes the last timed step's result
+partitions (key offsets, key bytes, counts) as ``DIR/<partition>.<column>.npy``;
+the corpus is a function of the arguments alone, so two builds can be compared
+file for file.
+
+With ``--full``, before the steady-state steps ONE cold iteration is timed
+from the split files on disk (page cache dropped with posix_fadvise, best
+effort) to the results in host memory — the shape of the reference's single
+49 s run, whose mapfns read their split files (examples/WordCount/mapfn.lua:4).
+It is reported as ``cold_first_iteration_ms`` next to the steady-state headline.
 Every rank reads and pins only its own splits (native loader, ops/io.py).
+``--full`` also compares every word's count with the generator's
+(``per_key_valid``) and prints the statistics block of the last step.
 
 The corpus is fixed, so adding GPUs divides it (strong scaling).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--from-files DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--from-files DIR]
 
 With N > 1 and no torchrun environment, the script starts the N ranks itself
 (``python -m torch.distributed.run --nproc-per-node N ...`` as a child process;
@@ -58,7 +67,13 @@ def parse_args(argv=None):
                     help="keep the corpus in HBM across steps (default: stage it from host memory every step)")
     ap.add_argument("--from-files", default=None, metavar="DIR",
                     help="corpus = the files in DIR (sorted; one split per file) instead of the synthetic one")
-    ap.add_argument("--no-cold", action="store_true", help="skip the cold file-to-result first iteration")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the cold file-to-result first iteration, the per-word comparison "
+                         "with the generator's counts and the statistics block of the last step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's result partitions as DIR/<name>.npy")
+    ap.add_argument("--no-cold", action="store_true",
+                    help="with --full: skip the cold file-to-result first iteration")
     ap.add_argument("--force-shuffle", action="store_true",
                     help="also time the W>1 data path (pack, count exchange, RCCL all_to_all_single, receive-side "
                          "reduce) at one GPU: a one-rank nccl group, reported as force_shuffle_ms_per_step")
@@ -159,11 +174,55 @@ def truth_counts(d: str) -> dict:
     return {vb[voff[i]:voff[i + 1]]: int(cnt[i]) for i in range(cnt.size)}
 
 
-def result_counts(eng, res) -> dict:
-    """word -> count from every rank's result partitions (on rank 0)."""
+DUMP_BUDGET_BYTES = 60 * 2**20  # --dump-outputs writes at most this much (the files stay under 64 MB in all)
+
+
+def dump_outputs(directory: str, gathered: list) -> None:
+    """The gathered result partitions (what a caller of the timed path holds
+    after a step) as ``directory/<partition>.<column>.npy``: key offsets,
+    key bytes, key hashes and counts, float32 where that is exact (<= 16-bit
+    integers, float32) and float64 otherwise; a 64-bit integer column that
+    float64 cannot hold exactly becomes its ``.high32`` and ``.low32`` halves.
+    Above the size budget every array is cut to the same fraction of its
+    elements, chosen by a fixed seed."""
+    import numpy as np
+    arrays = []
+    for name, cols in gathered:
+        for col, v in sorted(cols.items()):
+            parts = v if isinstance(v, (list, tuple)) else [v]
+            for i, a in enumerate(parts):
+                if hasattr(a, "cpu"):
+                    a = a.cpu().numpy()
+                if not isinstance(a, np.ndarray) or a.dtype.kind not in "biuf":
+                    continue
+                a = np.ascontiguousarray(a).reshape(-1)
+                tag = f"{name}.{col}" + (f".{i}" if len(parts) > 1 else "")
+                with np.errstate(invalid="ignore"):
+                    inexact = a.dtype.kind in "iu" and a.dtype.itemsize == 8 and \
+                        not np.array_equal(a.astype(np.float64).astype(a.dtype), a)
+                if inexact:
+                    # 64-bit patterns (key hashes) that float64 cannot hold: two exact 32-bit halves
+                    u = a.view(np.uint64)
+                    arrays.append((tag + ".high32", u >> np.uint64(32), np.float64))
+                    arrays.append((tag + ".low32", u & np.uint64(0xFFFFFFFF), np.float64))
+                    continue
+                small = a.dtype.itemsize <= 2 or a.dtype == np.float32
+                arrays.append((tag, a, np.float32 if small else np.float64))
+    total = sum(a.size * np.dtype(t).itemsize for _n, a, t in arrays)
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(1, total))
+    rng = np.random.default_rng(0)
+    os.makedirs(directory, exist_ok=True)
+    for tag, a, t in arrays:
+        if frac < 1.0:
+            a = a[np.sort(rng.choice(a.size, int(a.size * frac), replace=False))]
+        np.save(os.path.join(directory, tag + ".npy"), a.astype(t))
+
+
+def result_counts(gathered: list) -> dict:
+    """word -> count from every rank's gathered result partitions (on rank 0)."""
     import numpy as np
     out = {}
-    for _name, cols in eng.gather_results(res):
+    for _name, cols in gathered:
         off, blob, val = cols["key_off"], cols["key_blob"], cols["val"]
         b = blob.tobytes() if isinstance(blob, np.ndarray) else bytes(blob)
         for i in range(val.size):
@@ -235,7 +294,8 @@ def main() -> int:
     cold_tokens = None
     table_cap = 1 << 20
     store = None
-    if not args.no_cold:
+    dropped = False
+    if args.full and not args.no_cold:
         dropped = all(mio.drop_page_cache(p) for p in paths)
         D.barrier(device=device)
         sync()
@@ -305,7 +365,11 @@ def main() -> int:
     # download buffers until the next tail)
     counted = D.all_reduce_sum_int(last.total_value, device) if last is not None else 0
     distinct = D.all_reduce_sum_int(last.distinct_keys, device) if last is not None else 0
-    got = result_counts(eng, last) if last is not None else {}
+    gathered = eng.gather_results(last) if last is not None and (args.full or args.dump_outputs) else []
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered)
+    got = result_counts(gathered) if args.full else {}
+    del gathered
 
     fs_ms = fs_valid = None
     if args.force_shuffle:
@@ -330,17 +394,18 @@ def main() -> int:
         del e2, r2
 
     per_key = None
-    if rank == 0 and cdir is not None:
+    if args.full and rank == 0 and cdir is not None:
         per_key = got == truth_counts(cdir)
     if cdir is None:
         words = counted  # external files: the engine's own token count
-    block = eng.stats_block(last) if last is not None else ""  # a collective at W > 1: every rank
+    # (a collective at W > 1: every rank)
+    block = eng.stats_block(last) if args.full and last is not None else ""
     valid = True
     if rank == 0:
         print(block, file=sys.stderr, end="")
         print(f"# tokens counted {counted} (expected {words}), distinct words {distinct}, per-key match {per_key}, "
-              f"bytes {total_bytes}, per-phase s: {last.timings}, cold first iteration ms {cold_ms} "
-              f"(tokens {cold_tokens}, page cache dropped {not args.no_cold and dropped})",
+              f"bytes {total_bytes}, per-phase s: {last.timings if last is not None else None}, "
+              f"cold first iteration ms {cold_ms} (tokens {cold_tokens}, page cache dropped {dropped})",
               file=sys.stderr, flush=True)
         valid = counted == words and per_key is not False and (cold_tokens is None or cold_tokens == words) and \
             fs_valid is not False

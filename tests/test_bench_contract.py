@@ -24,7 +24,8 @@ def _run(cmd):
 
 @pytest.mark.parametrize("n", [1, 2])
 def test_bench_json_contract_cpu(n):
-    args = ["bench.py", "--gpus", str(n), "--steps", "2", "--warmup", "1", "--lines", "4000", "--words", "60000"]
+    args = ["bench.py", "--gpus", str(n), "--steps", "2", "--warmup", "1", "--lines", "4000", "--words", "60000",
+            "--full"]
     if n == 1:
         out = _run([sys.executable] + args)
     else:
@@ -40,11 +41,40 @@ def test_bench_json_contract_cpu(n):
     assert out["cold_first_iteration_ms"] > 0
 
 
+def test_bench_plain_run_and_dump_outputs_cpu(tmp_path):
+    """A plain run times exactly ``--steps`` steps and measures nothing besides
+    (no cold iteration, no per-word comparison); ``--dump-outputs`` writes the
+    last step's result partitions as float32/float64 ``.npy`` files, the same
+    from run to run, that hold the word count."""
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        out = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--lines", "4000",
+                    "--words", "60000", "--dump-outputs", str(tmp_path / d)])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["config"]["valid"] is True
+        assert out["value"] == pytest.approx(60000 / (out["ms_per_step"] / 1000.0))
+        assert out["cold_first_iteration_ms"] is None and out["config"]["per_key_valid"] is None
+        outs.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = outs
+    assert list(a) == list(b) and len(a) >= 30  # 10 partitions x (key_off, key_blob, val)
+    assert all(f.endswith(".npy") and a[f].dtype in (np.float32, np.float64) for f in a)
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2**20
+    vals = [a[f] for f in a if f.endswith(".val.npy")]
+    assert len(vals) == 10 and sum(float(v.sum()) for v in vals) == 60000
+    words = set()
+    for f in a:
+        if f.endswith(".key_blob.npy"):
+            off, blob = a[f.replace("key_blob", "key_off")].astype(np.int64), a[f].astype(np.uint8).tobytes()
+            words |= {blob[off[i]:off[i + 1]] for i in range(off.size - 1)}
+    assert len(words) == sum(v.size for v in vals)
+
+
 def test_bench_spawns_its_own_ranks_cpu():
     """``python bench.py --gpus 2`` with no torchrun environment starts the two
     ranks itself and relays rank 0's single JSON line (the driver's N>1 form
     must never silently measure one rank)."""
     out = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--lines", "4000",
-                "--words", "60000"])
+                "--words", "60000", "--full"])
     assert out["n_gpus"] == 2 and out["world"] == 2 and out["backend"] == "gloo"
     assert out["config"]["valid"] is True and out["config"]["per_key_valid"] is True

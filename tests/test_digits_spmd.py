@@ -18,7 +18,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 DM = "lua_mapreduce_1_amd.examples.DigitsMLP"
-REF_PNG = "/root/reference/misc/digits.png"
+# a copy of the reference's misc/digits.png
+REF_PNG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "digits.png")
 EPOCHS = 4
 
 
@@ -31,7 +32,7 @@ def _free_port():
 
 
 def _data_arg():
-    return REF_PNG if os.path.exists(REF_PNG) else "synthetic"
+    return REF_PNG
 
 
 def run_digits(device, data, epochs=EPOCHS, force_shuffle=False):

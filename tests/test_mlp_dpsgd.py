@@ -8,6 +8,7 @@ curve is unpinned; what is pinned is the math (autograd) and that the three
 execution forms (1 rank, W ranks, server/worker jobs) agree."""
 import contextlib
 import io
+import os
 import socket
 import threading
 
@@ -235,10 +236,10 @@ def test_graph_epochs_equal_eager(gpu):
     assert [h["va_loss"] for h in rg["history"]] == [h["va_loss"] for h in re_["history"]]
 
 
-REF_PNG = "/root/reference/misc/digits.png"
+# a copy of the reference's misc/digits.png
+REF_PNG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "digits.png")
 
 
-@pytest.mark.skipif(not __import__("os").path.exists(REF_PNG), reason="reference digits.png not present")
 def test_reference_digits_png_trains():
     """The reference's own dataset (misc/digits.png: 100 rows x 10 glyphs of
     16x16, read as pixels only), the APRIL-ANN schedule until the stopping rule

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${1:-rehearse}
 mkdir -p $OUT
 for n in 2 4; do
-  timeout -k 10 300 python3 bench.py --gpus $n --steps 5 --warmup 2 --no-cold > $OUT/bench_gpus$n.log 2>&1 || exit $?
+  timeout -k 10 300 python3 bench.py --gpus $n --steps 5 --warmup 2 --full --no-cold > $OUT/bench_gpus$n.log 2>&1 || exit $?
   echo "gpus=$n $(tail -1 $OUT/bench_gpus$n.log | grep -o '"ms_per_step": [0-9.]*\|"valid": [a-z]*\|"per_key_valid": [a-z]*\|"backend": "[a-z-]*"' | paste -sd' ')"
 done
 # result downloads: the runtime's blit vs our copy kernel on a few workgroups

@@ -23,6 +23,13 @@ for the workers of ONE node:
 
 Without a GPU the arena chunks are files in ``/dev/shm`` (the same protocol
 between host processes), so the storage is testable on a CPU-only machine.
+On a node that mixes both kinds of worker, a GPU reducer reads a CPU
+worker's ``/dev/shm`` files too (staged through pinned host memory into its
+pull buffer); a worker without a GPU cannot read a file that lives in a
+GPU's memory and fails that job with an error that says so.  Only a fold
+whose files are all columnar (``rows >= 0`` in every descriptor) is decoded
+on the device; record files of a host map are read to the host and merged
+there.
 
 Lifetime: an owner keeps its chunks until its worker starts the map phase of
 a later iteration or finishes the task (every reduce of the iteration has then
@@ -150,9 +157,13 @@ class HBMStore:
                     c.mm[off:off + len(data)] = data
             out = []
             for name, data, c, off in placed:
-                rows = struct.unpack_from("<Q", data, 4)[0] if data[:4] == b"MRC1" else -1
+                # an MRC1 file's header counts (rows, key bytes): a reducer checks them against len
+                # before its decode kernel trusts them; any other file: -1
+                rows = nb = -1
+                if len(data) >= 20 and data[:4] == b"MRC1":
+                    rows, nb = struct.unpack_from("<qq", data, 4)
                 d = {"host": self.host, "pid": self.pid, "dev": self._device.index if self._gpu() else -1,
-                     "c": c.cid, "h": c.handle.hex(), "off": off, "len": len(data), "rows": rows}
+                     "c": c.cid, "h": c.handle.hex(), "off": off, "len": len(data), "rows": rows, "nb": nb}
                 out.append((name, MAGIC + json.dumps(d, separators=(",", ":")).encode()))
                 self.stats["puts"] += 1
                 self.stats["put_bytes"] += len(data)
@@ -248,6 +259,11 @@ class HBMStore:
             finally:
                 os.close(fd)
         else:
+            import torch
+            if not torch.cuda.is_available():
+                raise RuntimeError(f"hbm storage: a map file is in the memory of GPU {d['dev']} (owner pid {d['pid']}) "
+                                   f"and this process has no GPU to read it with (run this worker on a GPU, or use "
+                                   f"gridfs or shared storage on a node that mixes CPU and GPU workers)")
             from ..ops import _hip
             p = ctypes.c_void_p()
             rc = _hip.lib().mr_ipc_open(ctypes.create_string_buffer(h, 64), ctypes.byref(p))
@@ -304,12 +320,34 @@ class HBMStore:
             bases.append(off)
             total = off + d["len"]
         buf = torch.empty(max(total, 16), dtype=torch.uint8, device=device)
-        srcs = []
+        srcs: list = []
+        hosted = []  # (index, bytes) of files in a host arena (/dev/shm chunks of a worker without a GPU)
         with self._lock:
             self._gpu()
-            for d in ds:
+            for i, d in enumerate(ds):
                 c = self._local_chunk(d)
-                srcs.append((c.ptr if c is not None else self._peer(d)) + d["off"])
+                src = (c.mm if c.ptr is None else c.ptr) if c is not None else self._peer(d)
+                if isinstance(src, mmap.mmap):
+                    hosted.append((i, src[d["off"]:d["off"] + d["len"]]))
+                    srcs.append(0)
+                else:
+                    srcs.append(src + d["off"])
+        staged = None
+        if hosted:
+            # host files go up in one copy (pinned staging, each at 4 mod 16 like its place in buf,
+            # so the gather copy below moves them with 16-byte vectors too)
+            hb, htotal = [], 0
+            for _i, b in hosted:
+                off = (htotal + 15) // 16 * 16 + ALIGN_MOD
+                hb.append(off)
+                htotal = off + len(b)
+            stage = torch.empty(max(htotal, 16), dtype=torch.uint8, pin_memory=True)
+            a = stage.numpy()
+            for off, (_i, b) in zip(hb, hosted):
+                a[off:off + len(b)] = np.frombuffer(b, np.uint8)
+            staged = stage.to(device, non_blocking=True)
+            for off, (i, _b) in zip(hb, hosted):
+                srcs[i] = staged.data_ptr() + off
         chunk = int(_hip.lib().mr_gather_copy_chunk())
         lens = np.array([d["len"] for d in ds], np.uint64)
         nch = (lens + np.uint64(chunk - 1)) // np.uint64(chunk)
@@ -322,7 +360,8 @@ class HBMStore:
         _hip.call("mr_gather_copy", _hip.ptr(t), len(ds), int(nch.sum()), _hip.stream(device))
         self.stats["pulls"] += len(ds)
         self.stats["pull_bytes"] += int(lens.sum())
-        buf._mr_keep = t  # the copy table lives until the buffer does (stream order)
+        # the copy table and the staged host files live until the buffer does (stream order)
+        buf._mr_keep = (t, staged)
         return buf, bases, ds
 
 

@@ -412,9 +412,9 @@ class job:  # noqa: N801
                     from . import hbm_store
                     if not all(hbm_store.is_descriptor(b) for b in blobs):
                         raise RuntimeError("hbm storage: a map file's descriptor is missing")
-                    if dev_op in FOLD_OPS and dev.default_device().type == "cuda":
+                    if _hbm_route(blobs, dev_op in FOLD_OPS, dev.default_device().type == "cuda") == "pull":
                         pulled = blobs  # the files stay on the device (pulled peer to peer below)
-                    else:
+                    else:  # (host-map MRK1 files among them: the magic check below sends these to the host merge)
                         blobs = hbm_store.store().read_many(blobs)
                 magic = codec.MAGIC_COL2 if cols_op else codec.MAGIC_COL
                 if pulled is None and not all(b[:4] == magic for b in blobs):
@@ -475,9 +475,53 @@ def _aligned_bases(lens) -> tuple[list[int], int]:
     return bases, total
 
 
-def _decode_files(buf: torch.Tensor, bases: list[int], rows: list[int]):
+def _hbm_route(descs: list[bytes], fold: bool, on_gpu: bool) -> str:
+    """How a reduce job reads its ``hbm`` map files: ``"pull"`` (they stay on
+    the device: gather copy + MRC1 decode) only for a fold on a GPU whose
+    files are ALL columnar — a descriptor of an MRC1 file carries its row
+    count, every other file's (the host map's MRK1 records) ``rows = -1``.
+    Otherwise ``"read"``: the bytes come to the host, where the magic check
+    picks the device fold or the host merge."""
+    from . import hbm_store
+    if fold and on_gpu and all(hbm_store.HBMStore.parse(x).get("rows", -1) >= 0 for x in descs):
+        return "pull"
+    return "read"
+
+
+def _check_mrc1_layout(size: int, bases, rows, lens, key_bytes) -> None:
+    """Host-side check of everything the decode kernel will index: it reads
+    ``rows[j]`` rows of four 8-byte columns behind file j's header without a
+    bound of its own.  ValueError when a row count is negative (not an MRC1
+    file), a header does not account for the file's length, or a file does
+    not lie inside the buffer at 4 mod 8."""
+    if not (len(bases) == len(rows) == len(lens) == len(key_bytes)):
+        raise ValueError("MRC1 decode: bases, rows, lens and key_bytes differ in length")
+    for j, (b, n, ln, nb) in enumerate(zip(bases, rows, lens, key_bytes)):
+        b, n, ln, nb = int(b), int(n), int(ln), int(nb)
+        if n < 0 or nb < 0:
+            raise ValueError(f"MRC1 decode: file {j} has row count {n} (not a columnar file)")
+        if 20 + 8 * (4 * n + 1) + nb != ln:
+            raise ValueError(f"MRC1 decode: file {j} of {ln} bytes cannot hold {n} rows and {nb} key bytes")
+        if b < 0 or b % 8 != 4 or b + ln > size:
+            raise ValueError(f"MRC1 decode: file {j} at {b} (+{ln}) is misplaced in a buffer of {size} bytes")
+
+
+def _mrc1_header(blob) -> tuple[int, int]:
+    """(rows, key bytes) an MRC1 file's header declares; (-1, -1) for any
+    other file."""
+    if len(blob) < 20 or bytes(blob[:4]) != codec.MAGIC_COL:
+        return -1, -1
+    n, nb = np.frombuffer(blob, np.int64, 2, 4)
+    return int(n), int(nb)
+
+
+def _decode_files(buf: torch.Tensor, bases: list[int], rows: list[int], lens: list[int], key_bytes: list[int]):
     """MRC1 files at ``bases`` of one device buffer -> (hi, lo, val, rep)
-    columns, ONE launch (csrc/hip/ipc.hip); rep words index ``buf``."""
+    columns, ONE launch (csrc/hip/ipc.hip); rep words index ``buf``.
+    ``rows`` / ``key_bytes``: what each file's header declares, ``lens``: the
+    files' sizes; checked against each other before anything is allocated or
+    launched."""
+    _check_mrc1_layout(buf.numel(), bases, rows, lens, key_bytes)
     from ..ops import _hip
     d = buf.device
     rstart = np.zeros(len(rows) + 1, np.int64)
@@ -506,7 +550,8 @@ def _device_reduce_hbm(descs: list[bytes], op: str) -> bytes:
     from . import hbm_store
     d = dev.default_device()
     buf, bases, ds = hbm_store.store().pull_device(descs, d)
-    hi, lo, val, rep = _decode_files(buf, bases, [x["rows"] for x in ds])
+    hi, lo, val, rep = _decode_files(buf, bases, [x.get("rows", -1) for x in ds], [x["len"] for x in ds],
+                                     [x.get("nb", -1) for x in ds])
     return _reduce_device_cols(hi, lo, val, rep, buf, op)
 
 
@@ -517,14 +562,16 @@ def _device_reduce(blobs: list[bytes], op: str) -> bytes:
     there by one launch."""
     d = dev.default_device()
     if d.type == "cuda":
-        bases, total = _aligned_bases([len(b) for b in blobs])
+        lens = [len(b) for b in blobs]
+        bases, total = _aligned_bases(lens)
+        heads = [_mrc1_header(b) for b in blobs]
+        rows, key_bytes = [h[0] for h in heads], [h[1] for h in heads]
         stage = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True)
         a = stage.numpy()
         for off, b in zip(bases, blobs):
             a[off:off + len(b)] = np.frombuffer(b, np.uint8)
         buf = stage.to(d, non_blocking=True)
-        rows = [int(np.frombuffer(b, np.uint64, 1, 4)[0]) for b in blobs]
-        hi, lo, val, rep = _decode_files(buf, bases, rows)
+        hi, lo, val, rep = _decode_files(buf, bases, rows, lens, key_bytes)
         return _reduce_device_cols(hi, lo, val, rep, buf, op)
     cols = [codec.decode_columnar(b) for b in blobs]
     n = sum(int(c["hi"].size) for c in cols)

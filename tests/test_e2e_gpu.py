@@ -25,3 +25,19 @@ def test_wordcount_device_plane_on_gpu(gpu, cs, storage, scenario):
     assert got == naive_output()
     assert s.last_stats["failed_map_jobs"] == 0 and s.last_stats["failed_red_jobs"] == 0
     assert devmod.STATS.get("maps_cuda", 0) - before == 4  # every map job on the GPU
+
+
+@pytest.mark.parametrize("scenario", ["combiner_aci", "general_reducer"])
+def test_wordcount_host_map_hbm_on_gpu(gpu, cs, scenario):
+    """``hbm`` storage with the host map (task ``device="host"``) and GPU
+    reducers: the map files are MRK1 records in the device arena, their
+    descriptors carry ``rows = -1``.  A fold reduce (combiner_aci:
+    ``device_reduce = "sum"``) must not send them to the MRC1 decode kernel:
+    it reads them back (one gather copy, one download) and merges on the
+    host, like every other storage."""
+    before = devmod.STATS.get("maps_cuda", 0)
+    p = dict(SCENARIOS[scenario], storage="hbm", device="host")
+    got, s = run_job(cs, f"wcgpu_hostmap_hbm_{scenario}", p, nworkers=2)
+    assert got == naive_output()
+    assert s.last_stats["failed_map_jobs"] == 0 and s.last_stats["failed_red_jobs"] == 0
+    assert devmod.STATS.get("maps_cuda", 0) == before  # no map job on the GPU

@@ -11,14 +11,24 @@
 // node maps the arena (hipIpcOpenMemHandle) and pulls the files it needs with
 // ONE gather-copy launch over xGMI (or inside the GPU) into its own buffer, where
 // ONE decode launch turns the columnar files (runtime/codec.py MRC1) into the
-// reduce table's input columns.  No byte of the intermediate data goes through
-// host memory or the coordinator's socket.
+// reduce table's input columns.  The write side of a device fold map (word count
+// and the other fold ops of runtime/job.py::_run_device_map_locked on a GPU
+// worker) is its mirror: ONE plan launch sizes the partition files from the
+// sorted tail's columns, ONE encode launch writes them as MRC1 files straight
+// into the arena.  For those jobs no byte of the intermediate data goes through
+// host memory or the coordinator's socket: only the plan (partition row and
+// key-byte counts, the tail's flags: 8 * (2 * nparts + 4) bytes) comes to the
+// host.  The general plane's MRC2 / record files, host maps and a fold map whose
+// tail raised a flag are still encoded on the host and uploaded
+// (HBMStore.put_many); their reduce side stays on the device all the same.
 //
 //   mr_ipc_alloc / mr_ipc_free        hipMalloc'd arena chunks (exportable)
 //   mr_ipc_handle                     the 64-byte hipIpcMemHandle_t of a chunk
 //   mr_ipc_open / mr_ipc_close        a peer's chunk in this process
 //   mr_gather_copy                    n (src, dst, len) copies in one launch
 //   mr_mrc1_decode                    MRC1 files in one buffer -> hi, lo, val, rep
+//   mr_mrc1_plan                      partition counts + sorted offsets -> rows and key bytes per file
+//   mr_mrc1_encode                    sorted columns + key bytes -> every MRC1 file of a map job
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include "mr_common.h"
@@ -94,6 +104,142 @@ __global__ void __launch_bounds__(DC_T) mrc1_decode_kernel(const u8* __restrict_
   o_rep[r] = make_rep(kb + (u64)o, (u64)(koff[k + 1] - o));
 }
 
+// Rows and key bytes of every partition's file, and what the host needs to
+// decide whether the device may write them: out = i64 [2 * nparts + 4]:
+// rows[nparts] | key bytes[nparts] | bad | err | off[n] | sum of the counts.
+// bounds = the exclusive scan of the counts (clamped to n: counts of a sort that
+// gave up index nothing outside off's n + 1 entries).  One block; thread p sums
+// the p counts before its own from LDS (at most 255 broadcast reads: the
+// quadratic scan is deliberate, nparts <= 256 and a shuffle scan saves nothing
+// a launch of this size would show).
+constexpr int PL_T = 256;
+__global__ void __launch_bounds__(PL_T) mrc1_plan_kernel(const long long* __restrict__ counts,
+                                                         const long long* __restrict__ off, u64 n, u32 nparts,
+                                                         const u32* __restrict__ bad, const u32* __restrict__ err,
+                                                         long long* __restrict__ out) {
+  __shared__ u64 cnt[PL_T];
+  const u32 t = threadIdx.x;
+  cnt[t] = t < nparts ? (u64)counts[t] : 0;
+  __syncthreads();
+  u64 b0 = 0;
+  for (u32 q = 0; q < t; ++q) b0 += cnt[q];
+  u64 b1 = b0 + cnt[t];
+  if (t < nparts) {
+    const u64 a = b0 < n ? b0 : n, b = b1 < n ? b1 : n;
+    out[t] = (long long)cnt[t];
+    out[nparts + t] = off[b] - off[a];
+  }
+  if (t == PL_T - 1) {
+    out[2 * nparts] = (long long)bad[0];
+    out[2 * nparts + 1] = (long long)err[0];
+    out[2 * nparts + 2] = off[n];
+    out[2 * nparts + 3] = (long long)b1;
+  }
+}
+
+// One workgroup per EN_UNIT bytes of one file.  A file of n rows at dst
+// (dst % 16 == 4) is walked as the byte stream t = file offset + 4, so that
+// t % 16 == 0 is a 16-byte boundary of the destination: unit k of the file owns
+// t in [k * EN_UNIT, (k + 1) * EN_UNIT), a file of F bytes has
+// ceil((F + 4) / EN_UNIT) units (mr_mrc1_encode_units).  In stream terms:
+//   t = 4             "MRC1"
+//   t = 8 + 8 w       word w: n | nb | hi[n] | lo[n] | val[n] | key_off[n + 1]
+//   t = 32 + 32 n     key bytes (a 16-byte boundary)
+// Words go out as 8-byte stores.  Key bytes go out as 16-byte stores, every
+// unit's first one on a 16-byte boundary; their source blob + off[a] has any
+// alignment: each 16-byte piece is cut out of the two aligned 16-byte vectors
+// round it (the shift is the same for the whole unit), bytes only for the
+// file's last < 16 bytes and for a piece whose vectors would reach outside
+// [blob, blob + blob_cap).
+constexpr int EN_T = 256;
+constexpr u64 EN_UNIT = 1ull << 14;
+
+__device__ __forceinline__ uint4 cut16(uint4 lo, uint4 hi, u32 sh) {
+  // bytes sh .. sh + 15 of the 32 bytes lo | hi (0 < sh < 16)
+  const u64 x0 = (u64)lo.x | ((u64)lo.y << 32), x1 = (u64)lo.z | ((u64)lo.w << 32);
+  const u64 x2 = (u64)hi.x | ((u64)hi.y << 32), x3 = (u64)hi.z | ((u64)hi.w << 32);
+  const bool up = sh >= 8;
+  const u64 y0 = up ? x1 : x0, y1 = up ? x2 : x1, y2 = up ? x3 : x2;
+  const u32 r = (sh & 7) * 8;
+  const u64 o0 = r ? (y0 >> r) | (y1 << (64 - r)) : y0;
+  const u64 o1 = r ? (y1 >> r) | (y2 << (64 - r)) : y1;
+  return make_uint4((u32)o0, (u32)(o0 >> 32), (u32)o1, (u32)(o1 >> 32));
+}
+
+__global__ void __launch_bounds__(EN_T) mrc1_encode_kernel(const u64* __restrict__ hi, const u64* __restrict__ lo,
+                                                           const u64* __restrict__ val,
+                                                           const long long* __restrict__ off,
+                                                           const u8* __restrict__ blob, u64 blob_cap,
+                                                           const u64* __restrict__ dsts, const u64* __restrict__ rstart,
+                                                           const u64* __restrict__ rows,
+                                                           const u64* __restrict__ unit_start, u32 nfiles) {
+  const u64 c = blockIdx.x;
+  u32 flo = 0, fhi = nfiles;
+  while (fhi - flo > 1) {
+    const u32 mid = (flo + fhi) / 2;
+    if (unit_start[mid] <= c) flo = mid; else fhi = mid;
+  }
+  const u32 j = flo;
+  const u64 n = rows[j], a = rstart[j];
+  const u64 o0 = (u64)off[a];
+  const u64 nb = (u64)off[a + n] - o0;
+  const u64 tw = 32 + 32 * n;   // stream position of the key bytes
+  const u64 tend = tw + nb;     // ... and of the file's end
+  const u64 t0 = (c - unit_start[j]) * EN_UNIT;
+  if (t0 >= tend) return;
+  const u64 t1 = t0 + EN_UNIT < tend ? t0 + EN_UNIT : tend;
+  u8* base = reinterpret_cast<u8*>(dsts[j]) - 4;  // stream position 0: a 16-byte boundary
+  const u32 t = threadIdx.x;
+  if (t0 == 0 && t == 0) *reinterpret_cast<u32*>(base + 4) = 0x3143524Du;  // "MRC1"
+  if (t0 < tw) {
+    const u64 w0 = t0 ? (t0 - 8) / 8 : 0;
+    const u64 w1 = ((t1 < tw ? t1 : tw) - 8) / 8;
+    u64* dw = reinterpret_cast<u64*>(base + 8);
+    for (u64 w = w0 + t; w < w1; w += EN_T) {
+      u64 v;
+      if (w < 2) v = w ? nb : n;
+      else if (w < 2 + n) v = hi[a + (w - 2)];
+      else if (w < 2 + 2 * n) v = lo[a + (w - 2 - n)];
+      else if (w < 2 + 3 * n) v = val[a + (w - 2 - 2 * n)];
+      else v = (u64)off[a + (w - 2 - 3 * n)] - o0;
+      dw[w] = v;
+    }
+  }
+  if (t1 > tw) {
+    const u64 b0 = (t0 > tw ? t0 : tw) - tw, b1 = t1 - tw;  // key bytes [b0, b1) of the file; b0 % 16 == 0
+    u8* d = base + tw + b0;
+    const u64 so = o0 + b0;                                  // their offset in blob
+    const uintptr_t sa = (uintptr_t)blob + so;
+    const u32 sh = (u32)(sa & 15);
+    const u64 n16 = (b1 - b0) / 16;
+    const uintptr_t blo = (uintptr_t)blob, bhi = (uintptr_t)blob + blob_cap;
+    for (u64 k = t; k < n16; k += EN_T) {
+      const uintptr_t va = sa - sh + 16 * k;  // the aligned vector that holds the piece's first byte
+      uint4 o;
+      if (va >= blo && va + (sh ? 32 : 16) <= bhi) {
+        const uint4 x = *reinterpret_cast<const uint4*>(va);
+        o = sh ? cut16(x, *reinterpret_cast<const uint4*>(va + 16), sh) : x;
+      } else {
+        u32 w[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const u64 p = so + 16 * k + i;
+          const u32 byte = p < blob_cap ? blob[p] : 0u;
+          w[i >> 2] |= byte << (8 * (i & 3));
+        }
+        o = make_uint4(w[0], w[1], w[2], w[3]);
+      }
+      reinterpret_cast<uint4*>(d)[k] = o;
+    }
+    const u64 done = 16 * n16;
+    const u64 rem = b1 - b0 - done;  // < 16: the file's last bytes
+    if (t < rem) {
+      const u64 p = so + done + t;
+      d[done + t] = p < blob_cap ? blob[p] : (u8)0;
+    }
+  }
+}
+
 }  // namespace mr
 
 using namespace mr;
@@ -145,6 +291,39 @@ int mr_mrc1_decode(const void* buf, const void* meta, unsigned nfiles, unsigned 
   const u64 g = (nrows + DC_T - 1) / DC_T;
   hipLaunchKernelGGL(mrc1_decode_kernel, dim3((unsigned)g), dim3(DC_T), 0, s, (const u8*)buf, m, m + nfiles, nfiles,
                      nrows, (u64*)hi, (u64*)lo, (long long*)val, (u64*)rep);
+  return (int)hipGetLastError();
+}
+
+// out = device i64 [2 * nparts + 4] (mrc1_plan_kernel); counts = the tail's
+// partition counts, off = its n + 1 sorted key offsets, bad / err = its flags
+int mr_mrc1_plan(const void* counts, const void* off, unsigned long long n, unsigned nparts, const void* bad,
+                 const void* err, void* out, hipStream_t s) {
+  if (nparts == 0 || nparts > (unsigned)PL_T) return -1;
+  hipLaunchKernelGGL(mrc1_plan_kernel, dim3(1), dim3(PL_T), 0, s, (const long long*)counts, (const long long*)off,
+                     (u64)n, nparts, (const u32*)bad, (const u32*)err, (long long*)out);
+  return (int)hipGetLastError();
+}
+
+unsigned long long mr_mrc1_encode_unit() { return EN_UNIT; }
+
+// workgroups (units) of a file of file_bytes bytes: its stream starts 4 bytes
+// before the file, on a 16-byte boundary
+unsigned long long mr_mrc1_encode_units(unsigned long long file_bytes) {
+  return (file_bytes + 4 + EN_UNIT - 1) / EN_UNIT;
+}
+
+// plan = device u64 [4 * nfiles]: dst | row_start | rows | unit_start (the
+// launch's file list, uploaded by the caller; dst % 16 == 4, file j = rows
+// [row_start, row_start + rows) of the sorted columns); nunits = unit_start of
+// the last file + its units.  Every file of a map job in ONE launch.
+int mr_mrc1_encode(const void* hi, const void* lo, const void* val, const void* off, const void* blob,
+                   unsigned long long blob_cap, const void* plan, unsigned nfiles, unsigned long long nunits,
+                   hipStream_t s) {
+  if (nfiles == 0 || nunits == 0) return 0;
+  const u64* p = static_cast<const u64*>(plan);
+  hipLaunchKernelGGL(mrc1_encode_kernel, dim3((unsigned)nunits), dim3(EN_T), 0, s, (const u64*)hi, (const u64*)lo,
+                     (const u64*)val, (const long long*)off, (const u8*)blob, (u64)blob_cap, p, p + nfiles,
+                     p + 2 * nfiles, p + 3 * nfiles, nfiles);
   return (int)hipGetLastError();
 }
 

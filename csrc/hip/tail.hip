@@ -481,27 +481,15 @@ u64 mr_tail_ws_layout(u64 n, u32 nparts, u64 blob_cap, u64 cap, u64* off) {
 
 static u32 g_tail_epoch = 0;
 
-// n = occupied slots of the table; src = the key-byte source (map arena or the
-// received blob); hp / hb = pinned host buffers of the packed columns and the
-// key bytes; est >= 0: DMA min(est, hb_cap) key bytes, else a device-sized copy.
-// padded != 0: n is a row bound, not the count (tail_pad_kernel): the host
-// learns the count from the downloaded partition counts, and bits 3/4 of the
-// downloaded flag word if the bound was too small / the table overflowed.
-// gran: the sort's look-back granules, >= 256 * mr_onesweep_tiles(n) u64 of a
-// buffer that holds nothing else (zeroed when allocated).  They used to be a
-// region of ws, whose layout moves with n: a later tail's granule rows then lay
-// over an earlier tail's permutation words, whose top bits can read as a live
-// epoch tag — a late predecessor's granule was taken from that stale word and
-// the pass scattered with a wrong prefix, silently (seen with 4 worker
-// processes sharing one GPU, whose contention makes predecessors late, and
-// whose fresh processes run small epochs; profiles/r6/server_worker/).
-int mr_tail_run(void* tag, void* hi, void* lo, void* val, void* rep, void* ctrl, u64 cap, u64 n, u32 nparts,
-                const void* src, void* ws, void* gran, u64 blob_cap, void* hp, void* hb, long long est, u64 hb_cap,
-                int padded, hipStream_t s) {
-  if (gran == nullptr) return -1;
-  if (nparts > 256 || (padded && nparts > 255)) return -1;
-  u64 off[TB_COUNT];
-  mr_tail_ws_layout(n, nparts, blob_cap, cap, off);
+}  // extern "C"
+
+// The tail up to and including the key-byte gather, shared by mr_tail_run and
+// mr_tail_run_dev: afterwards the workspace holds the sorted HI / LO / VAL, the
+// 64-bit OFF[n + 1], the key bytes in BLOB, the partition counts at TZ_PCOUNT
+// and the flags at TZ_BAD / TZ_ERR.  off = the workspace layout.
+static int tail_sorted(void* tag, void* hi, void* lo, void* val, void* rep, void* ctrl, u64 cap, u64 n, u32 nparts,
+                       const void* src, void* ws, void* gran, u64 blob_cap, int padded, const u64* off,
+                       hipStream_t s) {
   u8* w = (u8*)ws;
   auto P = [&](int b) { return (void*)(w + off[b]); };
   u8* z = w + off[TB_ZERO];
@@ -548,6 +536,40 @@ int mr_tail_run(void* tag, void* hi, void* lo, void* val, void* rep, void* ctrl,
     if (rc) return rc;
     rc = mr_gather_key_bytes(P(TB_HI), P(TB_LO), P(TB_REP), offs, n, src, P(TB_BLOB), blob_cap ? blob_cap : 1, s);
   }
+  return rc;
+}
+
+extern "C" {
+
+int mr_mrc1_plan(const void* counts, const void* off, unsigned long long n, unsigned nparts, const void* bad,
+                 const void* err, void* out, hipStream_t s);
+
+// n = occupied slots of the table; src = the key-byte source (map arena or the
+// received blob); hp / hb = pinned host buffers of the packed columns and the
+// key bytes; est >= 0: DMA min(est, hb_cap) key bytes, else a device-sized copy.
+// padded != 0: n is a row bound, not the count (tail_pad_kernel): the host
+// learns the count from the downloaded partition counts, and bits 3/4 of the
+// downloaded flag word if the bound was too small / the table overflowed.
+// gran: the sort's look-back granules, >= 256 * mr_onesweep_tiles(n) u64 of a
+// buffer that holds nothing else (zeroed when allocated).  They used to be a
+// region of ws, whose layout moves with n: a later tail's granule rows then lay
+// over an earlier tail's permutation words, whose top bits can read as a live
+// epoch tag — a late predecessor's granule was taken from that stale word and
+// the pass scattered with a wrong prefix, silently (seen with 4 worker
+// processes sharing one GPU, whose contention makes predecessors late, and
+// whose fresh processes run small epochs; profiles/r6/server_worker/).
+int mr_tail_run(void* tag, void* hi, void* lo, void* val, void* rep, void* ctrl, u64 cap, u64 n, u32 nparts,
+                const void* src, void* ws, void* gran, u64 blob_cap, void* hp, void* hb, long long est, u64 hb_cap,
+                int padded, hipStream_t s) {
+  if (gran == nullptr) return -1;
+  if (nparts > 256 || (padded && nparts > 255)) return -1;
+  u64 off[TB_COUNT];
+  mr_tail_ws_layout(n, nparts, blob_cap, cap, off);
+  u8* w = (u8*)ws;
+  auto P = [&](int b) { return (void*)(w + off[b]); };
+  u8* z = w + off[TB_ZERO];
+  long long* offs = (long long*)P(TB_OFF);
+  int rc = tail_sorted(tag, hi, lo, val, rep, ctrl, cap, n, nparts, src, ws, gran, blob_cap, padded, off, s);
   if (rc) return rc;
   rc = mr_tail_pack(P(TB_VAL), offs, n, z + TZ_PCOUNT, nparts, z + TZ_BAD, z + TZ_ERR, P(TB_PACKED), s);
   if (rc) return rc;
@@ -560,6 +582,27 @@ int mr_tail_run(void* tag, void* hi, void* lo, void* val, void* rep, void* ctrl,
     rc = mr_copy_to_host(P(TB_BLOB), hb, offs + n, 1, hb_cap, s);
   }
   return rc;
+}
+
+// The tail of a map job whose files the device writes itself (mr_mrc1_encode,
+// ipc.hip): everything mr_tail_run does up to the key-byte gather, then
+// mr_mrc1_plan into `plan` (device i64 [2 * nparts + 4]) and ONE download of
+// it into the pinned `hplan`.  No packed download, no key-byte download; the
+// sorted columns stay in the workspace for the encode launch.  n is the row
+// count (no padded mode).
+int mr_tail_run_dev(void* tag, void* hi, void* lo, void* val, void* rep, void* ctrl, u64 cap, u64 n, u32 nparts,
+                    const void* src, void* ws, void* gran, u64 blob_cap, void* plan, void* hplan, hipStream_t s) {
+  if (gran == nullptr || plan == nullptr || hplan == nullptr) return -1;
+  if (nparts == 0 || nparts > 256) return -1;
+  u64 off[TB_COUNT];
+  mr_tail_ws_layout(n, nparts, blob_cap, cap, off);
+  u8* w = (u8*)ws;
+  u8* z = w + off[TB_ZERO];
+  int rc = tail_sorted(tag, hi, lo, val, rep, ctrl, cap, n, nparts, src, ws, gran, blob_cap, 0, off, s);
+  if (rc) return rc;
+  rc = mr_mrc1_plan(z + TZ_PCOUNT, w + off[TB_OFF], n, nparts, z + TZ_BAD, z + TZ_ERR, plan, s);
+  if (rc) return rc;
+  return mr_d2h_async(hplan, plan, 8 * (2 * (u64)nparts + 4), s);
 }
 
 }  // extern "C"

@@ -141,13 +141,18 @@ _SIGS = {
     "mr_gather_copy": [_p, _u32, _u64, _p],
     "mr_gather_copy_chunk": [],
     "mr_mrc1_decode": [_p, _p, _u32, _u64, _p, _p, _p, _p, _p],
+    "mr_mrc1_plan": [_p, _p, _u64, _u32, _p, _p, _p, _p],
+    "mr_mrc1_encode": [_p, _p, _p, _p, _p, _u64, _p, _u32, _u64, _p],
+    "mr_mrc1_encode_unit": [],
+    "mr_mrc1_encode_units": [_u64],
+    "mr_tail_run_dev": [_p, _p, _p, _p, _p, _p, _u64, _u64, _u32, _p, _p, _p, _u64, _p, _p, _p],
     "mr_wc3_set_dyn": [_i32],
     "mr_agg_set_batch": [_i32],
     "mr_agg_set_phases": [_i32],
 }
 _RESTYPE_U64 = {"mr_compact_pack_ws_bytes", "mr_ii_unique_tiles", "mr_text_tiles", "mr_scan_partials_len", "mr_tail_pack_bytes", "mr_tail_ws_layout",
                 "mr_tail_bhist_bytes", "mr_onesweep_tiles", "mr_rec_tie_ws_words", "mr_sdma_d2h_begin",
-                "mr_gather_copy_chunk"}
+                "mr_gather_copy_chunk", "mr_mrc1_encode_unit", "mr_mrc1_encode_units"}
 
 
 def lib():

@@ -559,7 +559,7 @@ def _tail_ws(d, n: int, nparts: int, blob_cap: int, cap: int):
         m = max(n, 1)
         i64 = lambda b, k: ws[o[_TB[b]]:o[_TB[b]] + 8 * k].view(torch.int64)  # noqa: E731
         v = {"args": tuple(i64(b, n) for b in ("HI0", "LO0", "VAL0", "REP0")), "hi": i64("HI", n), "lo": i64("LO", n),
-             "off": i64("OFF", m + 1), "blob": ws[o[_TB["BLOB"]]:o[_TB["BLOB"]] + max(blob_cap, 1)],
+             "val": i64("VAL", n), "off": i64("OFF", m + 1), "blob": ws[o[_TB["BLOB"]]:o[_TB["BLOB"]] + max(blob_cap, 1)],
              # (MR_DEBUG_TAIL: the packed download, the final permutation and sorted keys)
              "packed": ws[o[_TB["PACKED"]]:], "p1": ws[o[_TB["P1"]]:o[_TB["P1"]] + 4 * n],
              "k1": i64("K1", n), "c": i64("C", n), "zero": ws[o[_TB["ZERO"]]:o[_TB["ZERO"]] + 10512]}
@@ -763,6 +763,103 @@ def finalize_table(table, src, nparts: int, partition_module=None, need_keys: bo
                 cap = e.nbytes + e.nbytes // 4 + 4096
     hi, lo, val, rep = table.compact((n, ovf))
     return finalize(hi, lo, val, rep, src, nparts, partition_module, need_keys=need_keys)
+
+
+_ENC_UNIT: dict = {}  # "unit" -> bytes of a file's stream one encode workgroup writes (mr_mrc1_encode_unit)
+_ARENA_WS: dict = {}  # device -> buffers of finalize_table_to_arena (valid until its next call: it ends synchronised)
+
+
+def _arena_ws(d) -> dict:
+    w = _ARENA_WS.get(d)
+    if w is None:
+        w = _ARENA_WS[d] = {"plan": torch.zeros(2 * 256 + 4, dtype=torch.int64, device=d),
+                            "hplan": torch.zeros(2 * 256 + 4, dtype=torch.int64, pin_memory=True),
+                            "tab": torch.zeros(4 * 256, dtype=torch.int64, device=d),
+                            "htab": torch.zeros(4 * 256, dtype=torch.int64, pin_memory=True)}
+    return w
+
+
+def mrc1_file_plan(plan: np.ndarray, n: int, nparts: int, blob_cap: int):
+    """What the downloaded plan of ``mr_tail_run_dev`` (int64 [2 * nparts + 4]:
+    rows | key bytes | bad | err | off[n] | sum of the rows) allows: ``None``
+    when the device must not write the files — a flag of the tail is set (tie
+    run too long, unchecked long-key prefix tie: the host fix-up or the exact
+    re-sort decide the order; the sort gave up), the key bytes did not fit
+    the blob buffer, or the counts do not account for the n rows — else
+    ``(partitions, row starts, rows, key bytes, file sizes)`` of the non-empty
+    partitions' MRC1 files (int64 arrays)."""
+    plan = np.asarray(plan, np.int64)
+    rows, nbs = plan[:nparts], plan[nparts:2 * nparts]
+    bad, err, total_nb, total_rows = (int(x) for x in plan[2 * nparts:2 * nparts + 4])
+    if bad or err or total_nb > blob_cap or total_nb < 0:
+        return None
+    if total_rows != n or (rows < 0).any() or (nbs < 0).any() or int(nbs.sum()) != total_nb:
+        return None
+    starts = np.zeros(nparts, np.int64)
+    np.cumsum(rows[:-1], out=starts[1:])
+    parts = np.flatnonzero(rows > 0)
+    r, b = rows[parts], nbs[parts]
+    return parts, starts[parts], r, b, 28 + 32 * r + b
+
+
+def finalize_table_to_arena(table, src, nparts: int, partition_module, names_for, gen=None):
+    """A fold map's tail whose partition files never leave the device (``hbm``
+    storage): the native tail up to the key-byte gather and the file plan
+    (mr_tail_run_dev: ONE small download), places reserved in this process's
+    arena, ONE encode launch that writes every non-empty partition's MRC1
+    file into its place (mr_mrc1_encode, csrc/hip/ipc.hip) — byte for byte
+    what ``codec.encode_columnar`` makes of :func:`finalize_table`'s columns —
+    and the files' descriptors: ``[(names_for(p), descriptor)]`` in partition
+    order.  ``None`` when this path does not apply (the conditions of
+    :func:`finalize_table`'s native tail; an overflowed table) or must not be
+    trusted (:func:`mrc1_file_plan`): the caller runs :func:`finalize_table`,
+    which reads the same table.  Callers hold PLANE_LOCK."""
+    spec = getattr(partition_module, "device_partition", None) if partition_module is not None else ("fnv1", nparts)
+    if not (table.is_cuda and src is not None and spec is not None and spec[0] == "fnv1"
+            and int(spec[1]) == nparts and 0 < nparts <= 256 and table.device == default_device()):
+        return None
+    n, ovf = table.stats()
+    if ovf or n <= 0:
+        return None
+    from ..ops import _hip
+    from . import hbm_store
+    d = table.device
+    cap = src.numel()
+    ws, v = _tail_ws(d, n, nparts, cap, table.cap)
+    aw = _arena_ws(d)
+    s = _hip.stream(d)
+    _hip.call("mr_tail_run_dev", *table._gtab(), table.cap, n, nparts, _hip.ptr(src), _hip.ptr(ws),
+              _hip.ptr(_tail_gran(d, n)), cap, _hip.ptr(aw["plan"]), _hip.ptr(aw["hplan"]), s)
+    _hip.wait_stream(d)
+    plan_words = 2 * nparts + 4
+    got = mrc1_file_plan(aw["hplan"].numpy()[:plan_words], n, nparts, v["blob"].numel())
+    if got is None:
+        return None
+    parts, starts, rows, nbs, sizes = got
+    st = hbm_store.store()
+    if not st.on_gpu():  # (before anything is reserved: a place given out is arena space spent)
+        return None
+    unit = _ENC_UNIT.get("unit")
+    if unit is None:
+        unit = _ENC_UNIT["unit"] = int(_hip.lib().mr_mrc1_encode_unit())
+    units = (sizes + 4 + unit - 1) // unit  # (mr_mrc1_encode_units: a file's stream starts 4 bytes before it)
+    nf = int(sizes.size)
+    # the store's writer lock from the reservation to the publication: the places are raw device
+    # addresses, and another thread's write for a new generation would free the chunks under the launch
+    with st.writer():
+        places = st.reserve_many(sizes.tolist(), gen)
+        tab = aw["htab"].numpy()
+        tab[:nf] = np.array([pl.ptr for pl in places], np.uint64).view(np.int64)
+        tab[nf:2 * nf] = starts
+        tab[2 * nf:3 * nf] = rows
+        tab[3 * nf] = 0
+        np.cumsum(units[:-1], out=tab[3 * nf + 1:4 * nf])
+        _hip.call("mr_memcpy_async", _hip.ptr(aw["tab"]), _hip.ptr(aw["htab"]), 8 * 4 * nf, 1, s)
+        _hip.call("mr_mrc1_encode", _hip.ptr(v["hi"]), _hip.ptr(v["lo"]), _hip.ptr(v["val"]), _hip.ptr(v["off"]),
+                  _hip.ptr(v["blob"]), v["blob"].numel(), _hip.ptr(aw["tab"]), nf, int(units.sum()), s)
+        _hip.wait_stream(d)
+        return st.publish([names_for(int(p)) for p in parts], places, sizes.tolist(), rows.tolist(), nbs.tolist(),
+                          plan_bytes=8 * plan_words)
 
 
 def _unpack_fused(pend: dict):

@@ -16,8 +16,18 @@ for the workers of ONE node:
   and pulls the files it needs with ONE gather-copy launch (over xGMI when
   the owner sits on another GPU) into one device buffer; a columnar fold's
   files are then decoded into the reduce table's input columns by ONE kernel
-  (csrc/hip/ipc.hip) — the intermediate bytes never touch host memory or the
-  coordinator socket;
+  (csrc/hip/ipc.hip) — on the reduce side the intermediate bytes never touch
+  host memory or the coordinator socket;
+* the write side depends on who wrote the file.  A device fold map on a GPU
+  worker (``job._run_device_map_locked`` with ``MR_HBM_DEVICE_WRITE`` on)
+  reserves places in the arena (:meth:`HBMStore.reserve_many`), has ONE encode
+  launch write its MRC1 files there, and publishes them
+  (:meth:`HBMStore.publish`): only a plan of ``8 * (2 * nparts + 4)`` bytes
+  comes to the host, no byte of the files moves either way.  Every other
+  writer — the general plane's MRC2 and record files, a host map, a fold map
+  whose tail raised a flag — hands host ``bytes`` to :meth:`HBMStore.put_many`,
+  which stages them through pinned memory and uploads them
+  (``stats["staged_bytes"]`` counts these);
 * reduce results go to the coordinator like every storage's
   (job.lua:249-251: results always go to GridFS).
 
@@ -74,13 +84,31 @@ class _Chunk:
         self.mm = None       # host mapping (CPU arena)
 
 
+class Place:
+    """A file's reserved place in the owner's arena (:meth:`HBMStore.
+    reserve_many`): ``ptr`` = its device address (GPU arena; 4 mod 16), or
+    ``mem`` = the writable slice of the chunk's host mapping (CPU arena)."""
+    __slots__ = ("chunk", "off", "size")
+
+    def __init__(self, chunk: _Chunk, off: int, size: int):
+        self.chunk, self.off, self.size = chunk, off, size
+
+    @property
+    def ptr(self):
+        return None if self.chunk.ptr is None else self.chunk.ptr + self.off
+
+    @property
+    def mem(self):
+        return None if self.chunk.mm is None else memoryview(self.chunk.mm)[self.off:self.off + self.size]
+
+
 class HBMStore:
     """This process's arena (owner side) and its mapped peer chunks (reader
     side).  One per process; thread-safe (workers may be threads of one
     process)."""
 
     def __init__(self):
-        self._lock = threading.Lock()
+        self._lock = threading.RLock()  # (re-entrant: a device writer holds it round reserve_many .. publish)
         self._chunks: list[_Chunk] = []
         self._next = 0
         self._gen = None  # the (dbname, iteration) whose files the arena holds
@@ -88,7 +116,11 @@ class HBMStore:
         self.pid = os.getpid()
         self.host = utils.get_hostname()
         self._device = None
-        self.stats = {"puts": 0, "put_bytes": 0, "pulls": 0, "pull_bytes": 0, "opened": 0}
+        # puts / put_bytes: every file; staged_bytes: those that came as host bytes (put_many);
+        # dev_puts / dev_put_bytes: those a device writer put in place (reserve_many + publish),
+        # plan_bytes: what such writers downloaded to size them
+        self.stats = {"puts": 0, "put_bytes": 0, "pulls": 0, "pull_bytes": 0, "opened": 0, "staged_bytes": 0,
+                      "dev_puts": 0, "dev_put_bytes": 0, "plan_bytes": 0}
 
     # -- owner side -----------------------------------------------------------
     def _gpu(self):
@@ -145,10 +177,7 @@ class HBMStore:
         if not items:
             return []
         with self._lock:
-            if gen is not None and self._gen is not None and gen != self._gen:
-                self._release_locked()
-            if gen is not None:
-                self._gen = gen
+            self._enter_gen(gen)
             placed = [(name, data) + self._place(len(data)) for name, data in items]
             if self._gpu():
                 self._upload(placed)
@@ -162,11 +191,68 @@ class HBMStore:
                 rows = nb = -1
                 if len(data) >= 20 and data[:4] == b"MRC1":
                     rows, nb = struct.unpack_from("<qq", data, 4)
-                d = {"host": self.host, "pid": self.pid, "dev": self._device.index if self._gpu() else -1,
-                     "c": c.cid, "h": c.handle.hex(), "off": off, "len": len(data), "rows": rows, "nb": nb}
-                out.append((name, MAGIC + json.dumps(d, separators=(",", ":")).encode()))
-                self.stats["puts"] += 1
-                self.stats["put_bytes"] += len(data)
+                out.append((name, self._descriptor(c, off, len(data), rows, nb)))
+                self.stats["staged_bytes"] += len(data)
+            return out
+
+    def _enter_gen(self, gen) -> None:
+        if gen is not None and self._gen is not None and gen != self._gen:
+            self._release_locked()
+        if gen is not None:
+            self._gen = gen
+
+    def _descriptor(self, c: _Chunk, off: int, size: int, rows: int, nb: int) -> bytes:
+        d = {"host": self.host, "pid": self.pid, "dev": self._device.index if self._gpu() else -1,
+             "c": c.cid, "h": c.handle.hex(), "off": off, "len": size, "rows": rows, "nb": nb}
+        self.stats["puts"] += 1
+        self.stats["put_bytes"] += size
+        return MAGIC + json.dumps(d, separators=(",", ":")).encode()
+
+    def on_gpu(self) -> bool:
+        """True when this process's arena is device memory (places have ``ptr``)."""
+        with self._lock:
+            return self._gpu()
+
+    def writer(self):
+        """The store's lock as a context manager, for a writer that fills
+        reserved places through their raw addresses: held from
+        :meth:`reserve_many` to :meth:`publish` it keeps every other thread's
+        ``put_many`` / ``reserve_many`` — which release the arena when they
+        bring a new generation — out until the files are published, as
+        :meth:`put_many` does for its own copy.  Without it the places are
+        only safe while no other thread of the process writes."""
+        return self._lock
+
+    def reserve_many(self, sizes: list[int], gen=None) -> list[Place]:
+        """Places for files a writer fills itself (a device encode launch
+        through ``Place.ptr``; on a CPU arena ``Place.mem``), under
+        :meth:`put_many`'s rules: the arena of an earlier ``gen`` is released
+        first, files go back to back at 4 mod 16, one bigger than ``CHUNK``
+        gets a chunk of its own.  Nothing is readable before :meth:`publish`.
+        Hold :meth:`writer` from here to :meth:`publish` when other threads of
+        the process may write to the store meanwhile."""
+        with self._lock:
+            self._enter_gen(gen)
+            return [Place(c, off, int(n)) for n in sizes for c, off in (self._place(int(n)),)]
+
+    def publish(self, names: list[str], places: list[Place], sizes: list[int], rows: list[int], nbs: list[int],
+                plan_bytes: int = 0) -> list[tuple[str, bytes]]:
+        """(name, descriptor) pairs of files written into reserved places —
+        what :meth:`put_many` returns for the same bytes.  ``rows`` / ``nbs``:
+        the MRC1 header counts (-1 for any other file).  The writer has
+        finished (its stream is synchronised) before it publishes.
+        ``plan_bytes``: what it downloaded to size the files."""
+        if not (len(names) == len(places) == len(sizes) == len(rows) == len(nbs)):
+            raise ValueError("hbm storage: publish() lists differ in length")
+        with self._lock:
+            out = []
+            for name, pl, size, r, nb in zip(names, places, sizes, rows, nbs):
+                if int(size) != pl.size or pl.chunk not in self._chunks:
+                    raise RuntimeError(f"hbm storage: {name} does not fit its reserved place (or the arena was released)")
+                out.append((name, self._descriptor(pl.chunk, pl.off, pl.size, int(r), int(nb))))
+                self.stats["dev_puts"] += 1
+                self.stats["dev_put_bytes"] += pl.size
+            self.stats["plan_bytes"] += int(plan_bytes)
             return out
 
     def _upload(self, placed) -> None:

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .. import utils
-from ..utils import STATUS, TASK_STATUS
+from ..utils import STATUS, TASK_STATUS, config
 from ..utils.tuple import tuple as tuple_
 from . import codec, device as dev, fs as fsmod, modules
 
@@ -358,13 +358,26 @@ class job:  # noqa: N801
         modules.field(self.module, "device_mapfn")(map_key, map_value, ctx.emit)
         ctx.flush_host_pairs()
         self.mark_as_finished()
+        host = utils.get_hostname()
+        if (self.storage == "hbm" and _DUMP is None and config.TUNABLES.hbm_device_write
+                and dev.default_device().type == "cuda"):
+            # the partition files are written on the device, straight into this worker's arena
+            # (no download, host encode or upload); None: the tail raised a flag -> the host path below
+            descs = dev.finalize_table_to_arena(ctx.table, ctx.source(), nparts, pmod,
+                                                lambda p: f"{self.path}/{self.results_ns}.P{p}.M{map_key}",
+                                                gen=self._gen())
+            if descs is not None:
+                index = [(INDEX_PREFIX + name + INDEX_SEP + host, b"") for name, _ in descs]
+                self.cnn.gridfs().store_many(descs + index)
+                elapsed = _time.process_time() - clock1
+                self.mark_as_written(elapsed)
+                return elapsed
         cols = dev.finalize_table(ctx.table, ctx.source(), nparts, pmod, need_keys=True)
         # every storage's build replaces an existing file (BLOB_PUT overwrites,
         # file builders rename over), so the reference's remove-before-build
         # (job.lua:217-221) is one round trip per file with no effect; with the
         # coordinator blob store, all partition files and their index entries
         # of this job go in ONE request
-        host = utils.get_hostname()
         outputs, index = [], []
         for p in range(nparts):
             if cols["bounds"][p + 1] == cols["bounds"][p]:

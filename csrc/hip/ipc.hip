@@ -10,17 +10,22 @@
 // the handle and the file's place in the arena; a reducer on any GPU of the
 // node maps the arena (hipIpcOpenMemHandle) and pulls the files it needs with
 // ONE gather-copy launch over xGMI (or inside the GPU) into its own buffer, where
-// ONE decode launch turns the columnar files (runtime/codec.py MRC1) into the
-// reduce table's input columns.  The write side of a device fold map (word count
-// and the other fold ops of runtime/job.py::_run_device_map_locked on a GPU
-// worker) is its mirror: ONE plan launch sizes the partition files from the
-// sorted tail's columns, ONE encode launch writes them as MRC1 files straight
-// into the arena.  For those jobs no byte of the intermediate data goes through
+// ONE decode launch turns the columnar files (runtime/codec.py MRC1, or MRC2 for
+// the general plane's typed folds) into the reduce table's input columns.  The
+// write side of a device map on a GPU worker is its mirror.  A fold map (word
+// count and the other fold ops of runtime/job.py::_run_device_map_locked): ONE
+// plan launch sizes the partition files from the sorted tail's columns, ONE
+// encode launch writes them as MRC1 files straight into the arena.  A typed-fold
+// map (runtime/job.py::_run_generic_map, a column spec such as
+// ("f64:mean", "f64:max", "count")): the same plan launch over the sorted
+// columns of parallel/generic.py::order_fold, ONE encode launch that writes the
+// MRC2 files.  For those jobs no byte of the intermediate data goes through
 // host memory or the coordinator's socket: only the plan (partition row and
 // key-byte counts, the tail's flags: 8 * (2 * nparts + 4) bytes) comes to the
-// host.  The general plane's MRC2 / record files, host maps and a fold map whose
-// tail raised a flag are still encoded on the host and uploaded
-// (HBMStore.put_many); their reduce side stays on the device all the same.
+// host.  The general plane's record files (value lists), host maps, a fold map
+// whose tail raised a flag and a typed fold past the plan's limits are still
+// encoded on the host and uploaded (HBMStore.put_many); the reduce side of the
+// columnar ones stays on the device all the same.
 //
 //   mr_ipc_alloc / mr_ipc_free        hipMalloc'd arena chunks (exportable)
 //   mr_ipc_handle                     the 64-byte hipIpcMemHandle_t of a chunk
@@ -29,6 +34,8 @@
 //   mr_mrc1_decode                    MRC1 files in one buffer -> hi, lo, val, rep
 //   mr_mrc1_plan                      partition counts + sorted offsets -> rows and key bytes per file
 //   mr_mrc1_encode                    sorted columns + key bytes -> every MRC1 file of a map job
+//   mr_mrc2_decode                    MRC2 files in one buffer -> hi, lo, rep, k typed value columns
+//   mr_mrc2_encode                    sorted columns + key bytes -> every MRC2 file of a map job
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include "mr_common.h"
@@ -166,6 +173,41 @@ __device__ __forceinline__ uint4 cut16(uint4 lo, uint4 hi, u32 sh) {
   return make_uint4((u32)o0, (u32)(o0 >> 32), (u32)o1, (u32)(o1 >> 32));
 }
 
+// len key bytes from blob + so to d (d % 16 == 0): 16-byte stores cut out of the
+// aligned source vectors, bytes for the last < 16 and for a piece whose vectors
+// would reach outside [blob, blob + blob_cap).  One workgroup, thread t of EN_T.
+__device__ __forceinline__ void put_key_bytes(u8* __restrict__ d, const u8* __restrict__ blob, u64 blob_cap, u64 so,
+                                              u64 len, u32 t) {
+  const uintptr_t sa = (uintptr_t)blob + so;
+  const u32 sh = (u32)(sa & 15);
+  const u64 n16 = len / 16;
+  const uintptr_t blo = (uintptr_t)blob, bhi = (uintptr_t)blob + blob_cap;
+  for (u64 k = t; k < n16; k += EN_T) {
+    const uintptr_t va = sa - sh + 16 * k;  // the aligned vector that holds the piece's first byte
+    uint4 o;
+    if (va >= blo && va + (sh ? 32 : 16) <= bhi) {
+      const uint4 x = *reinterpret_cast<const uint4*>(va);
+      o = sh ? cut16(x, *reinterpret_cast<const uint4*>(va + 16), sh) : x;
+    } else {
+      u32 w[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const u64 p = so + 16 * k + i;
+        const u32 byte = p < blob_cap ? blob[p] : 0u;
+        w[i >> 2] |= byte << (8 * (i & 3));
+      }
+      o = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    reinterpret_cast<uint4*>(d)[k] = o;
+  }
+  const u64 done = 16 * n16;
+  const u64 rem = len - done;  // < 16: the file's last bytes
+  if (t < rem) {
+    const u64 p = so + done + t;
+    d[done + t] = p < blob_cap ? blob[p] : (u8)0;
+  }
+}
+
 __global__ void __launch_bounds__(EN_T) mrc1_encode_kernel(const u64* __restrict__ hi, const u64* __restrict__ lo,
                                                            const u64* __restrict__ val,
                                                            const long long* __restrict__ off,
@@ -207,36 +249,178 @@ __global__ void __launch_bounds__(EN_T) mrc1_encode_kernel(const u64* __restrict
   }
   if (t1 > tw) {
     const u64 b0 = (t0 > tw ? t0 : tw) - tw, b1 = t1 - tw;  // key bytes [b0, b1) of the file; b0 % 16 == 0
-    u8* d = base + tw + b0;
-    const u64 so = o0 + b0;                                  // their offset in blob
-    const uintptr_t sa = (uintptr_t)blob + so;
-    const u32 sh = (u32)(sa & 15);
-    const u64 n16 = (b1 - b0) / 16;
-    const uintptr_t blo = (uintptr_t)blob, bhi = (uintptr_t)blob + blob_cap;
-    for (u64 k = t; k < n16; k += EN_T) {
-      const uintptr_t va = sa - sh + 16 * k;  // the aligned vector that holds the piece's first byte
-      uint4 o;
-      if (va >= blo && va + (sh ? 32 : 16) <= bhi) {
-        const uint4 x = *reinterpret_cast<const uint4*>(va);
-        o = sh ? cut16(x, *reinterpret_cast<const uint4*>(va + 16), sh) : x;
-      } else {
-        u32 w[4] = {0, 0, 0, 0};
+    put_key_bytes(base + tw + b0, blob, blob_cap, o0 + b0, b1 - b0, t);
+  }
+}
+
+// MRC2 (codec.encode_columns): the typed folds' files.  k <= MRC2_MAXK value
+// columns of dtype code 0 = i64, 1 = f64 (8 bytes a value), 2 = f32 (4 bytes);
+// with k <= 8 the header is 36 bytes: "MRC2" n nb k | 8 code bytes.  A file at
+// 4 mod 8 has its hi, lo and key_off words aligned; a value column behind an
+// f32 column of odd n lies at 4 mod 8, and so may the key bytes.
+constexpr int MRC2_MAXK = 8;
+struct Mrc2Cols {
+  void* col[MRC2_MAXK];  // encode: the sorted source columns; decode: the output columns
+  u32 code[MRC2_MAXK];
+  u32 k;
+};
+
+__device__ __forceinline__ u32 mrc2_width(u32 code) { return code == 2 ? 4u : 8u; }
+
+// The 4-byte word at byte p (p % 4 == 0) of a file's value region (its k
+// columns of n values back to back), read from rows a .. a + n of the source
+// columns
+__device__ __forceinline__ u32 mrc2_value_word(const Mrc2Cols& cs, u64 n, u64 a, u64 p) {
+  u32 v = 0;
+  bool found = false;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const u64 p = so + 16 * k + i;
-          const u32 byte = p < blob_cap ? blob[p] : 0u;
-          w[i >> 2] |= byte << (8 * (i & 3));
-        }
-        o = make_uint4(w[0], w[1], w[2], w[3]);
+  for (int c = 0; c < MRC2_MAXK; ++c) {
+    if ((u32)c < cs.k && !found) {
+      const u32 w = mrc2_width(cs.code[c]);
+      const u64 sz = n * w;
+      if (p < sz) {
+        v = *reinterpret_cast<const u32*>(static_cast<const u8*>(cs.col[c]) + a * w + p);
+        found = true;
+      } else {
+        p -= sz;
       }
-      reinterpret_cast<uint4*>(d)[k] = o;
     }
-    const u64 done = 16 * n16;
-    const u64 rem = b1 - b0 - done;  // < 16: the file's last bytes
-    if (t < rem) {
-      const u64 p = so + done + t;
-      d[done + t] = p < blob_cap ? blob[p] : (u8)0;
+  }
+  return v;
+}
+
+// MRC2 files at base[j] of buf (base[j] % 8 == 4) -> hi, lo, rep and the k
+// typed value columns of rows rstart[j] .. rstart[j + 1]; every file has the
+// same k and codes (cs).  rep indexes buf, as in mrc1_decode_kernel.  A value
+// column at 4 mod 8 is read in 4-byte halves.
+__global__ void __launch_bounds__(DC_T) mrc2_decode_kernel(const u8* __restrict__ buf, const u64* __restrict__ base,
+                                                           const u64* __restrict__ rstart, u32 nfiles, u64 nrows,
+                                                           u64* __restrict__ o_hi, u64* __restrict__ o_lo,
+                                                           u64* __restrict__ o_rep, const Mrc2Cols cs) {
+  const u64 r = (u64)blockIdx.x * DC_T + threadIdx.x;
+  if (r >= nrows) return;
+  u32 lo = 0, hi = nfiles;
+  while (hi - lo > 1) {
+    const u32 mid = (lo + hi) / 2;
+    if (rstart[mid] <= r) lo = mid; else hi = mid;
+  }
+  const u64 n = rstart[lo + 1] - rstart[lo];
+  const u64 i = r - rstart[lo];
+  const u64 b = base[lo] + 36;
+  const u64* col = reinterpret_cast<const u64*>(buf + b);
+  const long long* koff = reinterpret_cast<const long long*>(col + 2 * n);
+  const long long o = koff[i];
+  o_hi[r] = col[i];
+  o_lo[r] = col[n + i];
+  u64 vb = b + 8 * (3 * n + 1);  // the value columns, then the key bytes
+#pragma unroll
+  for (int c = 0; c < MRC2_MAXK; ++c) {
+    if ((u32)c < cs.k) {
+      if (mrc2_width(cs.code[c]) == 4) {
+        static_cast<u32*>(cs.col[c])[r] = *reinterpret_cast<const u32*>(buf + vb + 4 * i);
+        vb += 4 * n;
+      } else {
+        const u8* s = buf + vb + 8 * i;
+        u64 v;
+        if (vb & 7) {
+          const u32* h = reinterpret_cast<const u32*>(s);
+          v = (u64)h[0] | ((u64)h[1] << 32);
+        } else {
+          v = *reinterpret_cast<const u64*>(s);
+        }
+        static_cast<u64*>(cs.col[c])[r] = v;
+        vb += 8 * n;
+      }
     }
+  }
+  o_rep[r] = make_rep(vb + (u64)o, (u64)(koff[i + 1] - o));
+}
+
+// One workgroup per EN_UNIT bytes of one MRC2 file, walked like an MRC1 file as
+// the stream t = file offset + 4 (dst % 16 == 4):
+//   t = 4               "MRC2"
+//   t = 8 + 8 w         word w: n | nb | k | codes | hi[n] | lo[n] | key_off[n + 1]
+//   t = 48 + 24 n       the value region: n * (sum of the widths) bytes, a multiple of 4
+//   t = tk              key bytes (tk % 16 is 0, 4, 8 or 12)
+// Words go out as 8-byte stores.  The value region goes out in 8-byte slots of
+// the stream too, each put together from two 4-byte loads of the columns' 8- or
+// 4-byte values (a column behind an odd f32 column is at 4 mod 8 in the file
+// and aligned in its source: no wide access is misaligned on either side), a
+// last half slot as 4 bytes.  Key bytes: bytes up to the first 16-byte boundary of
+// the destination (only behind tk, at most 12), then as in the MRC1 files.
+__global__ void __launch_bounds__(EN_T) mrc2_encode_kernel(const u64* __restrict__ hi, const u64* __restrict__ lo,
+                                                           const long long* __restrict__ off,
+                                                           const u8* __restrict__ blob, u64 blob_cap,
+                                                           const u64* __restrict__ dsts, const u64* __restrict__ rstart,
+                                                           const u64* __restrict__ rows,
+                                                           const u64* __restrict__ unit_start, u32 nfiles,
+                                                           const Mrc2Cols cs) {
+  const u64 c = blockIdx.x;
+  u32 flo = 0, fhi = nfiles;
+  while (fhi - flo > 1) {
+    const u32 mid = (flo + fhi) / 2;
+    if (unit_start[mid] <= c) flo = mid; else fhi = mid;
+  }
+  const u32 j = flo;
+  const u64 n = rows[j], a = rstart[j];
+  const u64 o0 = (u64)off[a];
+  const u64 nb = (u64)off[a + n] - o0;
+  u64 wsum = 0, codes = 0;
+#pragma unroll
+  for (int q = 0; q < MRC2_MAXK; ++q) {
+    if ((u32)q < cs.k) {
+      wsum += mrc2_width(cs.code[q]);
+      codes |= (u64)(cs.code[q] & 0xFF) << (8 * q);
+    }
+  }
+  const u64 tv = 48 + 24 * n;     // stream position of the value region,
+  const u64 tk = tv + n * wsum;   // ... of the key bytes
+  const u64 tend = tk + nb;       // ... and of the file's end
+  const u64 t0 = (c - unit_start[j]) * EN_UNIT;
+  if (t0 >= tend) return;
+  const u64 t1 = t0 + EN_UNIT < tend ? t0 + EN_UNIT : tend;
+  u8* base = reinterpret_cast<u8*>(dsts[j]) - 4;  // stream position 0: a 16-byte boundary
+  const u32 t = threadIdx.x;
+  if (t0 == 0 && t == 0) *reinterpret_cast<u32*>(base + 4) = 0x3243524Du;  // "MRC2"
+  if (t0 < tv) {
+    const u64 w0 = t0 ? (t0 - 8) / 8 : 0;
+    const u64 w1 = ((t1 < tv ? t1 : tv) - 8) / 8;
+    u64* dw = reinterpret_cast<u64*>(base + 8);
+    for (u64 w = w0 + t; w < w1; w += EN_T) {
+      u64 v;
+      if (w < 4) v = w == 0 ? n : w == 1 ? nb : w == 2 ? (u64)cs.k : codes;
+      else if (w < 4 + n) v = hi[a + (w - 4)];
+      else if (w < 4 + 2 * n) v = lo[a + (w - 4 - n)];
+      else v = (u64)off[a + (w - 4 - 2 * n)] - o0;
+      dw[w] = v;
+    }
+  }
+  if (t1 > tv && t0 < tk) {
+    // bytes [v0, v1) of the value region: v0 % 8 == 0; v1 % 8 == 4 only at the region's end
+    const u64 v0 = (t0 > tv ? t0 : tv) - tv, v1 = (t1 < tk ? t1 : tk) - tv;
+    const u64 nslots = (v1 - v0 + 7) / 8;
+    u8* d = base + tv;
+    for (u64 s = t; s < nslots; s += EN_T) {
+      const u64 p = v0 + 8 * s;
+      const u32 x0 = mrc2_value_word(cs, n, a, p);
+      if (p + 4 < v1) {
+        const u32 x1 = mrc2_value_word(cs, n, a, p + 4);
+        *reinterpret_cast<u64*>(d + p) = (u64)x0 | ((u64)x1 << 32);
+      } else {
+        *reinterpret_cast<u32*>(d + p) = x0;
+      }
+    }
+  }
+  if (t1 > tk) {
+    const u64 b0 = (t0 > tk ? t0 : tk) - tk, b1 = t1 - tk;  // key bytes [b0, b1) of the file
+    u8* d = base + tk + b0;
+    u64 head = (16 - ((tk + b0) & 15)) & 15;  // != 0 only when b0 == 0: every later unit starts on a boundary
+    if (head > b1 - b0) head = b1 - b0;
+    if (t < head) {
+      const u64 p = o0 + b0 + t;
+      d[t] = p < blob_cap ? blob[p] : (u8)0;
+    }
+    put_key_bytes(d + head, blob, blob_cap, o0 + b0 + head, b1 - b0 - head, t);
   }
 }
 
@@ -324,6 +508,45 @@ int mr_mrc1_encode(const void* hi, const void* lo, const void* val, const void* 
   hipLaunchKernelGGL(mrc1_encode_kernel, dim3((unsigned)nunits), dim3(EN_T), 0, s, (const u64*)hi, (const u64*)lo,
                      (const u64*)val, (const long long*)off, (const u8*)blob, (u64)blob_cap, p, p + nfiles,
                      p + 2 * nfiles, p + 3 * nfiles, nfiles);
+  return (int)hipGetLastError();
+}
+
+static bool mrc2_cols_ok(const Mrc2Cols* cs) {
+  if (cs == nullptr || cs->k < 1 || cs->k > (u32)MRC2_MAXK) return false;
+  for (u32 c = 0; c < cs->k; ++c)
+    if (cs->code[c] > 2 || cs->col[c] == nullptr) return false;
+  return true;
+}
+
+// meta as for mr_mrc1_decode; cols = host Mrc2Cols: the k output columns (i64 /
+// f64 / f32 [nrows]) and the dtype codes every file has.  -1: k or a code the
+// kernels do not know.
+int mr_mrc2_decode(const void* buf, const void* meta, unsigned nfiles, unsigned long long nrows, void* hi, void* lo,
+                   void* rep, const void* cols, hipStream_t s) {
+  if (nrows == 0 || nfiles == 0) return 0;
+  const Mrc2Cols* cs = static_cast<const Mrc2Cols*>(cols);
+  if (!mrc2_cols_ok(cs)) return -1;
+  const u64* m = static_cast<const u64*>(meta);
+  const u64 g = (nrows + DC_T - 1) / DC_T;
+  hipLaunchKernelGGL(mrc2_decode_kernel, dim3((unsigned)g), dim3(DC_T), 0, s, (const u8*)buf, m, m + nfiles, nfiles,
+                     nrows, (u64*)hi, (u64*)lo, (u64*)rep, *cs);
+  return (int)hipGetLastError();
+}
+
+unsigned long long mr_mrc2_encode_unit() { return EN_UNIT; }
+
+// plan as for mr_mrc1_encode (a file of n rows and nb key bytes has
+// 44 + 24 n + n * (sum of the widths) + nb bytes and ceil((bytes + 4) / unit)
+// units); cols = host Mrc2Cols: the k sorted value columns and their codes.
+int mr_mrc2_encode(const void* hi, const void* lo, const void* off, const void* blob, unsigned long long blob_cap,
+                   const void* cols, const void* plan, unsigned nfiles, unsigned long long nunits, hipStream_t s) {
+  if (nfiles == 0 || nunits == 0) return 0;
+  const Mrc2Cols* cs = static_cast<const Mrc2Cols*>(cols);
+  if (!mrc2_cols_ok(cs)) return -1;
+  const u64* p = static_cast<const u64*>(plan);
+  hipLaunchKernelGGL(mrc2_encode_kernel, dim3((unsigned)nunits), dim3(EN_T), 0, s, (const u64*)hi, (const u64*)lo,
+                     (const long long*)off, (const u8*)blob, (u64)blob_cap, p, p + nfiles, p + 2 * nfiles,
+                     p + 3 * nfiles, nfiles, *cs);
   return (int)hipGetLastError();
 }
 

@@ -145,6 +145,9 @@ _SIGS = {
     "mr_mrc1_encode": [_p, _p, _p, _p, _p, _u64, _p, _u32, _u64, _p],
     "mr_mrc1_encode_unit": [],
     "mr_mrc1_encode_units": [_u64],
+    "mr_mrc2_decode": [_p, _p, _u32, _u64, _p, _p, _p, _p, _p],
+    "mr_mrc2_encode": [_p, _p, _p, _p, _u64, _p, _p, _u32, _u64, _p],
+    "mr_mrc2_encode_unit": [],
     "mr_tail_run_dev": [_p, _p, _p, _p, _p, _p, _u64, _u64, _u32, _p, _p, _p, _u64, _p, _p, _p],
     "mr_wc3_set_dyn": [_i32],
     "mr_agg_set_batch": [_i32],
@@ -152,7 +155,32 @@ _SIGS = {
 }
 _RESTYPE_U64 = {"mr_compact_pack_ws_bytes", "mr_ii_unique_tiles", "mr_text_tiles", "mr_scan_partials_len", "mr_tail_pack_bytes", "mr_tail_ws_layout",
                 "mr_tail_bhist_bytes", "mr_onesweep_tiles", "mr_rec_tie_ws_words", "mr_sdma_d2h_begin",
-                "mr_gather_copy_chunk", "mr_mrc1_encode_unit", "mr_mrc1_encode_units"}
+                "mr_gather_copy_chunk", "mr_mrc1_encode_unit", "mr_mrc1_encode_units", "mr_mrc2_encode_unit"}
+
+MRC2_MAXK = 8  # value columns of an MRC2 file the device codec handles (csrc/hip/ipc.hip; ops/agg.py MAXC)
+MRC2_CODE = {torch.int64: 0, torch.float64: 1, torch.float32: 2}  # runtime/codec.py _DT_CODE
+MRC2_DTYPE = {v: k for k, v in MRC2_CODE.items()}
+
+
+class Mrc2Cols(ctypes.Structure):
+    """The value columns of ``mr_mrc2_encode`` (sources) / ``mr_mrc2_decode``
+    (outputs): device pointers and MRC2 dtype codes (csrc/hip/ipc.hip)."""
+    _fields_ = [("col", ctypes.c_void_p * MRC2_MAXK), ("code", ctypes.c_uint32 * MRC2_MAXK), ("k", ctypes.c_uint32)]
+
+
+def mrc2_cols(cols: list) -> Mrc2Cols:
+    """``Mrc2Cols`` of contiguous int64 / float64 / float32 tensors (1..8 of
+    them; the caller keeps them alive over the launch)."""
+    if not 1 <= len(cols) <= MRC2_MAXK:
+        raise ValueError(f"an MRC2 file on the device has 1..{MRC2_MAXK} value columns (got {len(cols)})")
+    a = Mrc2Cols()
+    a.k = len(cols)
+    for j, c in enumerate(cols):
+        if c.dtype not in MRC2_CODE:
+            raise ValueError(f"MRC2 value column {j}: dtype {c.dtype} is not int64, float64 or float32")
+        a.col[j] = ptr(c).value
+        a.code[j] = MRC2_CODE[c.dtype]
+    return a
 
 
 def lib():

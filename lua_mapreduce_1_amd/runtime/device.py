@@ -775,7 +775,8 @@ def _arena_ws(d) -> dict:
         w = _ARENA_WS[d] = {"plan": torch.zeros(2 * 256 + 4, dtype=torch.int64, device=d),
                             "hplan": torch.zeros(2 * 256 + 4, dtype=torch.int64, pin_memory=True),
                             "tab": torch.zeros(4 * 256, dtype=torch.int64, device=d),
-                            "htab": torch.zeros(4 * 256, dtype=torch.int64, pin_memory=True)}
+                            "htab": torch.zeros(4 * 256, dtype=torch.int64, pin_memory=True),
+                            "zero": torch.zeros(2, dtype=torch.int64, device=d)}  # flag words of a plan without a tail
     return w
 
 
@@ -860,6 +861,83 @@ def finalize_table_to_arena(table, src, nparts: int, partition_module, names_for
         _hip.wait_stream(d)
         return st.publish([names_for(int(p)) for p in parts], places, sizes.tolist(), rows.tolist(), nbs.tolist(),
                           plan_bytes=8 * plan_words)
+
+
+def mrc2_file_plan(plan: np.ndarray, n: int, nparts: int, blob_cap: int, width: int):
+    """:func:`mrc1_file_plan` for the MRC2 files of a typed fold whose value
+    columns take ``width`` bytes a row (the plan's flag words are zero: the
+    key order was exact): ``None`` when the counts do not account for the n
+    rows and their key bytes, else ``(partitions, row starts, rows, key bytes,
+    file sizes)`` of the non-empty partitions."""
+    got = mrc1_file_plan(plan, n, nparts, blob_cap)
+    if got is None:
+        return None
+    parts, starts, r, b, _ = got
+    return parts, starts, r, b, 44 + (24 + int(width)) * r + b
+
+
+def fold_columns_to_arena(out: dict, nparts: int, names_for, gen=None):
+    """A typed-fold map's partition files written on the device (``hbm``
+    storage), the twin of :func:`finalize_table_to_arena`.  ``out``: the
+    sorted device columns of ``parallel/generic.py::order_fold(...,
+    outputs=False)`` in exact (partition, key) order.  ONE plan launch
+    (mr_mrc1_plan over the partition counts and key offsets) and ONE small
+    download size the files, places are reserved in this process's arena, ONE
+    encode launch (mr_mrc2_encode, csrc/hip/ipc.hip) writes every non-empty
+    partition's MRC2 file into its place — byte for byte what
+    ``codec.encode_columns`` makes of ``host_partitions``' slices — and the
+    files' descriptors come back: ``[(names_for(p), descriptor)]`` in
+    partition order.  ``None`` when this path does not apply (no device
+    arena, more than 256 partitions or 8 columns, an inexact order, no key)
+    or the plan must not be trusted (:func:`mrc2_file_plan`); nothing is
+    reserved then, and the caller encodes the same ``out`` on the host.
+    Callers hold PLANE_LOCK."""
+    import ctypes
+    from ..ops import _hip
+    from . import hbm_store
+    hi, lo, off, blob, cols = out["hi"], out["lo"], out["key_off"], out["key_blob"], out["cols"]
+    n = int(hi.numel())
+    if not (hi.is_cuda and out.get("exact") and 0 < nparts <= 256 and 1 <= len(cols) <= _hip.MRC2_MAXK and n > 0
+            and hi.device == default_device() and all(c.dtype in _hip.MRC2_CODE for c in cols)
+            and hi.dtype == lo.dtype == off.dtype == torch.int64 and off.numel() == n + 1
+            and all(c.numel() == n for c in cols)):
+        return None
+    d = hi.device
+    aw = _arena_ws(d)
+    s = _hip.stream(d)
+    counts = out["counts"].to(torch.int64).contiguous()
+    _hip.call("mr_mrc1_plan", _hip.ptr(counts), _hip.ptr(off), n, nparts, _hip.ptr(aw["zero"]), _hip.ptr(aw["zero"]),
+              _hip.ptr(aw["plan"]), s)
+    plan_words = 2 * nparts + 4
+    width = sum(c.element_size() for c in cols)
+    got = mrc2_file_plan(ops.host_read(aw["plan"][:plan_words]), n, nparts, int(blob.numel()), width)
+    if got is None:
+        return None
+    parts, starts, rows, nbs, sizes = got
+    st = hbm_store.store()
+    if not st.on_gpu():  # (before anything is reserved: a place given out is arena space spent)
+        return None
+    unit = _ENC_UNIT.get("unit2")
+    if unit is None:
+        unit = _ENC_UNIT["unit2"] = int(_hip.lib().mr_mrc2_encode_unit())
+    units = (sizes + 4 + unit - 1) // unit  # (a file's stream starts 4 bytes before it)
+    nf = int(sizes.size)
+    codes = [_hip.MRC2_CODE[c.dtype] for c in cols]
+    with st.writer():  # (held from the reservation to the publication, as in finalize_table_to_arena)
+        places = st.reserve_many(sizes.tolist(), gen)
+        tab = aw["htab"].numpy()
+        tab[:nf] = np.array([pl.ptr for pl in places], np.uint64).view(np.int64)
+        tab[nf:2 * nf] = starts
+        tab[2 * nf:3 * nf] = rows
+        tab[3 * nf] = 0
+        np.cumsum(units[:-1], out=tab[3 * nf + 1:4 * nf])
+        _hip.call("mr_memcpy_async", _hip.ptr(aw["tab"]), _hip.ptr(aw["htab"]), 8 * 4 * nf, 1, s)
+        _hip.call("mr_mrc2_encode", _hip.ptr(hi), _hip.ptr(lo), _hip.ptr(off), _hip.ptr(blob), int(blob.numel()),
+                  ctypes.byref(_hip.mrc2_cols(cols)), _hip.ptr(aw["tab"]), nf, int(units.sum()), s)
+        _hip.wait_stream(d)
+        return st.publish([names_for(int(p)) for p in parts], places, sizes.tolist(), [-1] * nf, [-1] * nf,
+                          plan_bytes=8 * plan_words,
+                          mrc2=[{"rows": int(r), "nb": int(b), "codes": codes} for r, b in zip(rows, nbs)])
 
 
 def _unpack_fused(pend: dict):

@@ -18,15 +18,18 @@ for the workers of ONE node:
   files are then decoded into the reduce table's input columns by ONE kernel
   (csrc/hip/ipc.hip) — on the reduce side the intermediate bytes never touch
   host memory or the coordinator socket;
-* the write side depends on who wrote the file.  A device fold map on a GPU
-  worker (``job._run_device_map_locked`` with ``MR_HBM_DEVICE_WRITE`` on)
-  reserves places in the arena (:meth:`HBMStore.reserve_many`), has ONE encode
-  launch write its MRC1 files there, and publishes them
-  (:meth:`HBMStore.publish`): only a plan of ``8 * (2 * nparts + 4)`` bytes
-  comes to the host, no byte of the files moves either way.  Every other
-  writer — the general plane's MRC2 and record files, a host map, a fold map
-  whose tail raised a flag — hands host ``bytes`` to :meth:`HBMStore.put_many`,
-  which stages them through pinned memory and uploads them
+* the write side depends on who wrote the file.  A device map on a GPU
+  worker with ``MR_HBM_DEVICE_WRITE`` on — a fold map
+  (``job._run_device_map_locked``, MRC1 files) or a typed-fold map
+  (``job._run_generic_map`` with a column spec, MRC2 files) — reserves places
+  in the arena (:meth:`HBMStore.reserve_many`), has ONE encode launch write
+  its files there, and publishes them (:meth:`HBMStore.publish`): only a plan
+  of ``8 * (2 * nparts + 4)`` bytes comes to the host, no byte of the files
+  moves either way.  Every other writer — the general plane's record files
+  (value lists), a host map, a fold map whose tail raised a flag, a typed
+  fold the device codec does not take (more than 256 partitions, an inexact
+  key order) — hands host ``bytes`` to :meth:`HBMStore.put_many`, which
+  stages them through pinned memory and uploads them
   (``stats["staged_bytes"]`` counts these);
 * reduce results go to the coordinator like every storage's
   (job.lua:249-251: results always go to GridFS).
@@ -37,9 +40,10 @@ On a node that mixes both kinds of worker, a GPU reducer reads a CPU
 worker's ``/dev/shm`` files too (staged through pinned host memory into its
 pull buffer); a worker without a GPU cannot read a file that lives in a
 GPU's memory and fails that job with an error that says so.  Only a fold
-whose files are all columnar (``rows >= 0`` in every descriptor) is decoded
-on the device; record files of a host map are read to the host and merged
-there.
+whose files are all columnar (``rows >= 0`` in every descriptor: MRC1; an
+``mrc2`` entry in every descriptor: MRC2, whose ``rows`` stays -1) is decoded
+on the device from the pulled buffer; record files of a host map are read
+to the host and merged there.
 
 Lifetime: an owner keeps its chunks until its worker starts the map phase of
 a later iteration or finishes the task (every reduce of the iteration has then
@@ -62,11 +66,25 @@ from .. import utils
 
 MAGIC = b"MRH1"
 CHUNK = 64 << 20  # arena chunk (a bigger file gets a chunk of its own)
-ALIGN_MOD = 4     # files start at 4 mod 16: the 8-byte columns after MRC1's 20-byte header are aligned
+ALIGN_MOD = 4     # files start at 4 mod 16: the 8-byte columns after MRC1's 20-byte (MRC2's 36-byte) header are
+                  # aligned
 
 
 def is_descriptor(b) -> bool:
     return bool(b) and bytes(b[:4]) == MAGIC
+
+
+def mrc2_header(data) -> dict | None:
+    """``{"rows", "nb", "codes"}`` an MRC2 file's header declares
+    (runtime/codec.py ``encode_columns``), as its descriptor carries them; None
+    for any other file and for one with more than 8 value columns (its header
+    is longer than 36 bytes: the device codec does not take it)."""
+    if len(data) < 36 or bytes(data[:4]) != b"MRC2":
+        return None
+    n, nb, k = struct.unpack_from("<qqq", data, 4)
+    if not 1 <= k <= 8:
+        return None
+    return {"rows": n, "nb": nb, "codes": list(bytes(data[28:28 + k]))}
 
 
 def _shm_dir() -> str:
@@ -191,7 +209,7 @@ class HBMStore:
                 rows = nb = -1
                 if len(data) >= 20 and data[:4] == b"MRC1":
                     rows, nb = struct.unpack_from("<qq", data, 4)
-                out.append((name, self._descriptor(c, off, len(data), rows, nb)))
+                out.append((name, self._descriptor(c, off, len(data), rows, nb, mrc2_header(data))))
                 self.stats["staged_bytes"] += len(data)
             return out
 
@@ -201,9 +219,11 @@ class HBMStore:
         if gen is not None:
             self._gen = gen
 
-    def _descriptor(self, c: _Chunk, off: int, size: int, rows: int, nb: int) -> bytes:
+    def _descriptor(self, c: _Chunk, off: int, size: int, rows: int, nb: int, mrc2: dict | None = None) -> bytes:
         d = {"host": self.host, "pid": self.pid, "dev": self._device.index if self._gpu() else -1,
              "c": c.cid, "h": c.handle.hex(), "off": off, "len": size, "rows": rows, "nb": nb}
+        if mrc2 is not None:  # an MRC2 file's own counts and dtype codes (rows / nb above stay -1: not an MRC1 file)
+            d["mrc2"] = {"rows": int(mrc2["rows"]), "nb": int(mrc2["nb"]), "codes": [int(x) for x in mrc2["codes"]]}
         self.stats["puts"] += 1
         self.stats["put_bytes"] += size
         return MAGIC + json.dumps(d, separators=(",", ":")).encode()
@@ -236,20 +256,24 @@ class HBMStore:
             return [Place(c, off, int(n)) for n in sizes for c, off in (self._place(int(n)),)]
 
     def publish(self, names: list[str], places: list[Place], sizes: list[int], rows: list[int], nbs: list[int],
-                plan_bytes: int = 0) -> list[tuple[str, bytes]]:
+                plan_bytes: int = 0, mrc2: list | None = None) -> list[tuple[str, bytes]]:
         """(name, descriptor) pairs of files written into reserved places —
         what :meth:`put_many` returns for the same bytes.  ``rows`` / ``nbs``:
-        the MRC1 header counts (-1 for any other file).  The writer has
-        finished (its stream is synchronised) before it publishes.
-        ``plan_bytes``: what it downloaded to size the files."""
-        if not (len(names) == len(places) == len(sizes) == len(rows) == len(nbs)):
+        the MRC1 header counts (-1 for any other file).  ``mrc2``: per file
+        ``{"rows", "nb", "codes"}`` of an MRC2 file's header (:func:`mrc2_header`;
+        None for any other file).  The writer has finished (its stream is
+        synchronised) before it publishes.  ``plan_bytes``: what it downloaded
+        to size the files."""
+        if mrc2 is None:
+            mrc2 = [None] * len(names)
+        if not (len(names) == len(places) == len(sizes) == len(rows) == len(nbs) == len(mrc2)):
             raise ValueError("hbm storage: publish() lists differ in length")
         with self._lock:
             out = []
-            for name, pl, size, r, nb in zip(names, places, sizes, rows, nbs):
+            for name, pl, size, r, nb, m2 in zip(names, places, sizes, rows, nbs, mrc2):
                 if int(size) != pl.size or pl.chunk not in self._chunks:
                     raise RuntimeError(f"hbm storage: {name} does not fit its reserved place (or the arena was released)")
-                out.append((name, self._descriptor(pl.chunk, pl.off, pl.size, int(r), int(nb))))
+                out.append((name, self._descriptor(pl.chunk, pl.off, pl.size, int(r), int(nb), m2)))
                 self.stats["dev_puts"] += 1
                 self.stats["dev_put_bytes"] += pl.size
             self.stats["plan_bytes"] += int(plan_bytes)

@@ -308,13 +308,26 @@ class job:  # noqa: N801
         dev.STATS["maps_" + d.type] = dev.STATS.get("maps_" + d.type, 0) + 1
         self.mark_as_finished()
         src = gm.src.source()
+        host = utils.get_hostname()
         if kind == "cols":
             out = G.order_fold(*gm.table.compact(), src, nparts, pmod, phys, outputs=False)
+            if (self.storage == "hbm" and _DUMP is None and config.TUNABLES.hbm_device_write and d.type == "cuda"
+                    and out["exact"] and 0 < nparts <= 256 and len(out["cols"]) <= 8 and out["hi"].numel() > 0):
+                # the MRC2 partition files are written on the device, straight into this worker's arena
+                # (no download, host encode or upload); None: the plan was not trusted -> the host path below
+                descs = dev.fold_columns_to_arena(out, nparts,
+                                                  lambda p: f"{self.path}/{self.results_ns}.P{p}.M{map_key}",
+                                                  gen=self._gen())
+                if descs is not None:
+                    index = [(INDEX_PREFIX + name + INDEX_SEP + host, b"") for name, _ in descs]
+                    self.cnn.gridfs().store_many(descs + index)
+                    elapsed = _time.process_time() - clock1
+                    self.mark_as_written(elapsed)
+                    return elapsed
         else:
             space = gm.table.cap if gm.table.is_cuda else max(1, n)
             out = G.order_lists(*gm.table.postings(), src, nparts, pmod, spec == "concat_unique", dtype, space)
         parts = G.host_partitions(out, nparts, dtype)
-        host = utils.get_hostname()
         outputs, index = [], []
         for p, cols in sorted(parts.items()):
             name = f"{self.path}/{self.results_ns}.P{p}.M{map_key}"
@@ -425,7 +438,9 @@ class job:  # noqa: N801
                     from . import hbm_store
                     if not all(hbm_store.is_descriptor(b) for b in blobs):
                         raise RuntimeError("hbm storage: a map file's descriptor is missing")
-                    if _hbm_route(blobs, dev_op in FOLD_OPS, dev.default_device().type == "cuda") == "pull":
+                    on_gpu = dev.default_device().type == "cuda"
+                    if (_hbm_route(blobs, dev_op in FOLD_OPS, on_gpu) == "pull"
+                            or (cols_op and _hbm_route_cols(blobs, on_gpu) == "pull")):
                         pulled = blobs  # the files stay on the device (pulled peer to peer below)
                     else:  # (host-map MRK1 files among them: the magic check below sends these to the host merge)
                         blobs = hbm_store.store().read_many(blobs)
@@ -436,7 +451,7 @@ class job:  # noqa: N801
             if blobs is not None:
                 with dev.PLANE_LOCK:
                     if pulled is not None:
-                        out = _device_reduce_hbm(pulled, dev_op)
+                        out = _device_reduce_cols_hbm(pulled, dev_op) if cols_op else _device_reduce_hbm(pulled, dev_op)
                     else:
                         out = _device_reduce_cols(blobs, dev_op) if cols_op else _device_reduce(blobs, dev_op)
                 b.append(out)
@@ -499,6 +514,73 @@ def _hbm_route(descs: list[bytes], fold: bool, on_gpu: bool) -> str:
     if fold and on_gpu and all(hbm_store.HBMStore.parse(x).get("rows", -1) >= 0 for x in descs):
         return "pull"
     return "read"
+
+
+def _hbm_route_cols(descs: list[bytes], on_gpu: bool) -> str:
+    """:func:`_hbm_route` for a typed fold: ``"pull"`` (gather copy + MRC2
+    decode on the device) only on a GPU when EVERY descriptor carries an MRC2
+    file's counts (``mrc2``; its ``rows`` is -1, so :func:`_hbm_route` never
+    takes it for an MRC1 file).  Otherwise ``"read"``."""
+    from . import hbm_store
+    if on_gpu and descs and all(isinstance(hbm_store.HBMStore.parse(x).get("mrc2"), dict) for x in descs):
+        return "pull"
+    return "read"
+
+
+_MRC2_WIDTH = {0: 8, 1: 8, 2: 4}  # bytes of a value by dtype code (codec._DT_CODE: i64, f64, f32)
+
+
+def _check_mrc2_layout(size: int, bases, rows, lens, key_bytes, codes, want_codes) -> None:
+    """:func:`_check_mrc1_layout` for MRC2 files: the decode kernel reads
+    ``rows[j]`` rows of hi, lo, key_off and of ``len(want_codes)`` value
+    columns behind file j's 36-byte header without a bound of its own.
+    ``codes[j]``: the dtype codes file j declares, ``want_codes``: those of the
+    reduce spec's physical columns (the output columns the kernel writes).
+    ValueError for a negative count, 0 or more than 8 columns, an unknown
+    code, codes that differ between files or from ``want_codes``, a length
+    that is not ``44 + 24 n + n * (sum of the widths) + nb``, or a file that
+    does not lie inside the buffer at 4 mod 8."""
+    if not (len(bases) == len(rows) == len(lens) == len(key_bytes) == len(codes)):
+        raise ValueError("MRC2 decode: bases, rows, lens, key_bytes and codes differ in length")
+    want = [int(c) for c in want_codes]
+    if not 1 <= len(want) <= 8 or any(c not in _MRC2_WIDTH for c in want):
+        raise ValueError(f"MRC2 decode: the fold has column codes {want} (1..8 of {sorted(_MRC2_WIDTH)})")
+    for j, (b, n, ln, nb, cs) in enumerate(zip(bases, rows, lens, key_bytes, codes)):
+        b, n, ln, nb, cs = int(b), int(n), int(ln), int(nb), [int(c) for c in cs]
+        if n < 0 or nb < 0:
+            raise ValueError(f"MRC2 decode: file {j} has row count {n}, key bytes {nb} (not an MRC2 file)")
+        if not 1 <= len(cs) <= 8 or any(c not in _MRC2_WIDTH for c in cs):
+            raise ValueError(f"MRC2 decode: file {j} has column codes {cs} (1..8 of {sorted(_MRC2_WIDTH)})")
+        if cs != want:
+            raise ValueError(f"MRC2 decode: file {j} has column codes {cs}, the fold's columns are {want}")
+        if 44 + 24 * n + n * sum(_MRC2_WIDTH[c] for c in cs) + nb != ln:
+            raise ValueError(f"MRC2 decode: file {j} of {ln} bytes cannot hold {n} rows of columns {cs} and {nb} key "
+                             f"bytes")
+        if b < 0 or b % 8 != 4 or b + ln > size:
+            raise ValueError(f"MRC2 decode: file {j} at {b} (+{ln}) is misplaced in a buffer of {size} bytes")
+
+
+def _decode_cols_files(buf: torch.Tensor, bases: list[int], rows: list[int], lens: list[int], key_bytes: list[int],
+                       codes: list, want_codes: list[int]):
+    """MRC2 files at ``bases`` of one device buffer -> (hi, lo, rep, [typed
+    value columns]), ONE launch (csrc/hip/ipc.hip); rep words index ``buf``.
+    Everything the kernel will index is checked first
+    (:func:`_check_mrc2_layout`), before anything is allocated or launched."""
+    _check_mrc2_layout(buf.numel(), bases, rows, lens, key_bytes, codes, want_codes)
+    import ctypes
+    from ..ops import _hip
+    d = buf.device
+    rstart = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum(rows, out=rstart[1:])
+    n = int(rstart[-1])
+    meta = torch.from_numpy(np.concatenate([np.asarray(bases, np.int64), rstart])).to(d)
+    keys = torch.empty((3, max(n, 1)), dtype=torch.int64, device=d)
+    hi, lo, rep = (keys[i, :n] for i in range(3))
+    vals = [torch.empty(n, dtype=_hip.MRC2_DTYPE[int(c)], device=d) for c in want_codes]
+    if n:
+        _hip.call("mr_mrc2_decode", _hip.ptr(buf), _hip.ptr(meta), len(rows), n, _hip.ptr(hi), _hip.ptr(lo),
+                  _hip.ptr(rep), ctypes.byref(_hip.mrc2_cols(vals)), _hip.stream(d))
+    return hi, lo, rep, vals
 
 
 def _check_mrc1_layout(size: int, bases, rows, lens, key_bytes) -> None:
@@ -627,16 +709,51 @@ def ops_next_pow2(n: int) -> int:
     return 1 << max(0, (int(n) - 1).bit_length())
 
 
+def _spec_codes(phys) -> list[int]:
+    """MRC2 dtype codes of a fold's physical columns."""
+    return [codec._DT_CODE[np.dtype({"i64": np.int64, "f64": np.float64, "f32": np.float32}[dt])]
+            for dt, _op, _i in phys.cols]
+
+
+def _device_reduce_cols_hbm(descs: list[bytes], spec) -> bytes:
+    """``hbm`` storage, typed fold: the partition's MRC2 files are pulled from
+    the map workers' device arenas (peer to peer, one launch) and decoded on
+    the device (one launch) — no host copy of the intermediate data."""
+    from ..ops import agg as A
+    from . import hbm_store
+    phys = A.Physical(A.parse_spec(spec))
+    buf, bases, ds = hbm_store.store().pull_device(descs, dev.default_device())
+    m2 = [x.get("mrc2") or {} for x in ds]
+    hi, lo, rep, vals = _decode_cols_files(buf, bases, [m.get("rows", -1) for m in m2], [x["len"] for x in ds],
+                                           [m.get("nb", -1) for m in m2], [m.get("codes", []) for m in m2],
+                                           _spec_codes(phys))
+    return _fold_cols(phys, hi, lo, rep, vals, buf)
+
+
 def _device_reduce_cols(blobs: list[bytes], spec) -> bytes:
     """Merge ``MRC2`` partition files of a typed fold on the device: the
     partial physical columns of every key are folded again (a mean's sums
-    and counts add up) and the output columns written."""
+    and counts add up) and the output columns written.  On the GPU the files
+    go up as they are (one pinned staging copy, one H2D copy) and are decoded
+    there by one launch; on a CPU device they are decoded with numpy."""
     from ..ops import agg as A
-    from ..parallel import generic as G
+    from . import hbm_store
     phys = A.Physical(A.parse_spec(spec))
-    cols = [codec.decode_columns(b) for b in blobs]
     d = dev.default_device()
-    n = sum(int(c["hi"].size) for c in cols)
+    if d.type == "cuda":
+        lens = [len(b) for b in blobs]
+        bases, total = _aligned_bases(lens)
+        heads = [hbm_store.mrc2_header(b) or {} for b in blobs]
+        stage = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True)
+        a = stage.numpy()
+        for off, b in zip(bases, blobs):
+            a[off:off + len(b)] = np.frombuffer(b, np.uint8)
+        buf = stage.to(d, non_blocking=True)
+        hi, lo, rep, vals = _decode_cols_files(buf, bases, [h.get("rows", -1) for h in heads], lens,
+                                               [h.get("nb", -1) for h in heads], [h.get("codes", []) for h in heads],
+                                               _spec_codes(phys))
+        return _fold_cols(phys, hi, lo, rep, vals, buf)
+    cols = [codec.decode_columns(b) for b in blobs]
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)  # noqa: E731
     hi = t(np.concatenate([c["hi"] for c in cols]).view(np.int64))
     lo = t(np.concatenate([c["lo"] for c in cols]).view(np.int64))
@@ -646,6 +763,17 @@ def _device_reduce_cols(blobs: list[bytes], spec) -> bytes:
     rep = t(((offs << np.uint64(24)) | lens).view(np.int64))
     src = t(np.concatenate([c["key_blob"] for c in cols] + [np.zeros(1, np.uint8)]))
     vals = [t(np.concatenate([c["cols"][j] for c in cols])) for j in range(len(phys.cols))]
+    return _fold_cols(phys, hi, lo, rep, vals, src)
+
+
+def _fold_cols(phys, hi, lo, rep, vals: list, src) -> bytes:
+    """The rows of a typed fold's partition files (keys, rep words into
+    ``src``, one tensor per physical column) merged per key, ordered and
+    encoded as the partition's MRC2 result."""
+    from ..ops import agg as A
+    from ..parallel import generic as G
+    d = hi.device
+    n = int(hi.numel())
     merge = [(dt, op, j) for j, (dt, op, _i) in enumerate(phys.cols)]
     cap = max(1024, 4 * n)
     while True:

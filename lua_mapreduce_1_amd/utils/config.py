@@ -104,9 +104,10 @@ class Tunables:
                                "API, csrc/hip/sdma.hip) after the tail's kernels, not as a runtime blit kernel on "
                                "the CUs beside the next map (0 = never)")
     hbm_device_write: bool = _knob("MR_HBM_DEVICE_WRITE", True,
-                                   "hbm storage, device fold map on a GPU worker: the partition files are encoded "
-                                   "by one kernel straight into the worker's device arena (csrc/hip/ipc.hip "
-                                   "mr_mrc1_encode) instead of downloaded, encoded on the host and uploaded")
+                                   "hbm storage, device fold or typed-fold map on a GPU worker: the partition files "
+                                   "are encoded by one kernel straight into the worker's device arena (csrc/hip/"
+                                   "ipc.hip mr_mrc1_encode, mr_mrc2_encode for a column spec) instead of downloaded, "
+                                   "encoded on the host and uploaded")
     spin_us: float = _knob("MR_SPIN_US", 2000.0, "host spin on completion words before hipStreamSynchronize, us")
     rec_chunks: int = _knob("MR_REC_CHUNKS", 3,
                             "record plane at W > 1 (R <= W partitions, sampled splitters): rounds of the exchange "

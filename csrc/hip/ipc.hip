@@ -10,8 +10,9 @@
 // the handle and the file's place in the arena; a reducer on any GPU of the
 // node maps the arena (hipIpcOpenMemHandle) and pulls the files it needs with
 // ONE gather-copy launch over xGMI (or inside the GPU) into its own buffer, where
-// ONE decode launch turns the columnar files (runtime/codec.py MRC1, or MRC2 for
-// the general plane's typed folds) into the reduce table's input columns.  The
+// ONE decode launch turns the columnar files (runtime/codec.py MRC1, MRC2 for
+// the general plane's typed folds, MRL1 for its value lists) into the reduce
+// table's input columns.  The
 // write side of a device map on a GPU worker is its mirror.  A fold map (word
 // count and the other fold ops of runtime/job.py::_run_device_map_locked): ONE
 // plan launch sizes the partition files from the sorted tail's columns, ONE
@@ -19,13 +20,19 @@
 // map (runtime/job.py::_run_generic_map, a column spec such as
 // ("f64:mean", "f64:max", "count")): the same plan launch over the sorted
 // columns of parallel/generic.py::order_fold, ONE encode launch that writes the
-// MRC2 files.  For those jobs no byte of the intermediate data goes through
+// MRC2 files.  A list map (the same job without device_reduce or with a concat
+// op, scalar i64 / f64 values): ONE plan launch over order_lists' partition
+// counts, key offsets and list offsets, ONE encode launch that writes the MRL1
+// files (every key with its value list); its reducer decodes the pulled files
+// with ONE launch into rows and (value, row) pairs that the list-mode table
+// merges per key.  For those jobs no byte of the intermediate data goes through
 // host memory or the coordinator's socket: only the plan (partition row and
-// key-byte counts, the tail's flags: 8 * (2 * nparts + 4) bytes) comes to the
-// host.  The general plane's record files (value lists), host maps, a fold map
-// whose tail raised a flag and a typed fold past the plan's limits are still
-// encoded on the host and uploaded (HBMStore.put_many); the reduce side of the
-// columnar ones stays on the device all the same.
+// key-byte counts, the tail's flags: 8 * (2 * nparts + 4) bytes; a list map's
+// rows, key bytes and values: 8 * (3 * nparts + 3) bytes) comes to the host.
+// List maps with tuple or byte-string values (MRK1 records), host maps, a fold
+// map whose tail raised a flag and a typed fold or list map past the plan's
+// limits are still encoded on the host and uploaded (HBMStore.put_many); the
+// reduce side of the columnar ones stays on the device all the same.
 //
 //   mr_ipc_alloc / mr_ipc_free        hipMalloc'd arena chunks (exportable)
 //   mr_ipc_handle                     the 64-byte hipIpcMemHandle_t of a chunk
@@ -36,6 +43,9 @@
 //   mr_mrc1_encode                    sorted columns + key bytes -> every MRC1 file of a map job
 //   mr_mrc2_decode                    MRC2 files in one buffer -> hi, lo, rep, k typed value columns
 //   mr_mrc2_encode                    sorted columns + key bytes -> every MRC2 file of a map job
+//   mr_mrl1_plan                      partition counts + key and list offsets -> rows, key bytes, values per file
+//   mr_mrl1_encode                    sorted keys + value lists + key bytes -> every MRL1 file of a map job
+//   mr_mrl1_decode                    MRL1 files in one buffer -> hi, lo, rep per row; bits, row per value
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include "mr_common.h"
@@ -424,6 +434,165 @@ __global__ void __launch_bounds__(EN_T) mrc2_encode_kernel(const u64* __restrict
   }
 }
 
+// MRL1 (codec.encode_lists): the list maps' files: every key with its value
+// list (CSR: list_off / list_val, 8-byte words whose bits the kernels only
+// move; code 0 = i64, 1 = f64 says how a reader views them).  A file at 4 mod 8
+// has every word behind its 36-byte header aligned.
+//
+// The plan of a list map: out = i64 [3 * nparts + 3]:
+// rows[nparts] | key bytes[nparts] | values[nparts] | off[n] | loff[n] | sum of
+// the counts.  As in mrc1_plan_kernel the bounds are clamped to n, so counts
+// that do not add up index nothing outside the n + 1 entries of off and loff.
+__global__ void __launch_bounds__(PL_T) mrl1_plan_kernel(const long long* __restrict__ counts,
+                                                         const long long* __restrict__ off,
+                                                         const long long* __restrict__ loff, u64 n, u32 nparts,
+                                                         long long* __restrict__ out) {
+  __shared__ u64 cnt[PL_T];
+  const u32 t = threadIdx.x;
+  cnt[t] = t < nparts ? (u64)counts[t] : 0;
+  __syncthreads();
+  u64 b0 = 0;
+  for (u32 q = 0; q < t; ++q) b0 += cnt[q];
+  u64 b1 = b0 + cnt[t];
+  if (t < nparts) {
+    const u64 a = b0 < n ? b0 : n, b = b1 < n ? b1 : n;
+    out[t] = (long long)cnt[t];
+    out[nparts + t] = off[b] - off[a];
+    out[2 * nparts + t] = loff[b] - loff[a];
+  }
+  if (t == PL_T - 1) {
+    out[3 * nparts] = off[n];
+    out[3 * nparts + 1] = loff[n];
+    out[3 * nparts + 2] = (long long)b1;
+  }
+}
+
+// MRL1 files at base[j] of buf (base[j] % 8 == 4): file j holds rows
+// rstart[j] .. rstart[j + 1] and values vstart[j] .. vstart[j + 1] of the
+// output.  Thread i decodes row i (hi, lo, rep: rep indexes buf, as in
+// mrc1_decode_kernel) and value i (its bits and the global index of its row).
+// The value's row is the r of its file with list_off[r] <= k < list_off[r + 1]:
+// the LAST r with list_off[r] <= k, so runs of empty lists before it (equal
+// offsets) are passed over and those behind it never reached.  The search reads
+// list_off where it lies in buf: neighbouring values of a wave walk the same
+// upper levels (one address, broadcast) and end in neighbouring words, so the
+// loads stay in a few cache lines and nothing is staged in LDS.  Every index is
+// bounded by the counts the host checked (job._check_mrl1_layout), whatever
+// the offsets in the file say.
+__global__ void __launch_bounds__(DC_T) mrl1_decode_kernel(const u8* __restrict__ buf, const u64* __restrict__ base,
+                                                           const u64* __restrict__ rstart,
+                                                           const u64* __restrict__ vstart, u32 nfiles, u64 nrows,
+                                                           u64 nvals, u64* __restrict__ o_hi, u64* __restrict__ o_lo,
+                                                           u64* __restrict__ o_rep, u64* __restrict__ o_vbits,
+                                                           long long* __restrict__ o_vrow) {
+  const u64 i = (u64)blockIdx.x * DC_T + threadIdx.x;
+  if (i < nrows) {
+    u32 lo = 0, hi = nfiles;
+    while (hi - lo > 1) {
+      const u32 mid = (lo + hi) / 2;
+      if (rstart[mid] <= i) lo = mid; else hi = mid;
+    }
+    const u64 n = rstart[lo + 1] - rstart[lo];
+    const u64 nv = vstart[lo + 1] - vstart[lo];
+    const u64 k = i - rstart[lo];
+    const u64 b = base[lo] + 36;
+    const u64* col = reinterpret_cast<const u64*>(buf + b);
+    const long long* koff = reinterpret_cast<const long long*>(col + 2 * n);
+    const u64 kb = b + 8 * (4 * n + 2 + nv);  // the key bytes, behind list_off and list_val
+    const long long o = koff[k];
+    o_hi[i] = col[k];
+    o_lo[i] = col[n + k];
+    o_rep[i] = make_rep(kb + (u64)o, (u64)(koff[k + 1] - o));
+  }
+  if (i < nvals) {
+    u32 lo = 0, hi = nfiles;
+    while (hi - lo > 1) {
+      const u32 mid = (lo + hi) / 2;
+      if (vstart[mid] <= i) lo = mid; else hi = mid;
+    }
+    const u64 n = rstart[lo + 1] - rstart[lo];
+    const u64 k = i - vstart[lo];
+    const u64* col = reinterpret_cast<const u64*>(buf + base[lo] + 36);
+    const long long* loff = reinterpret_cast<const long long*>(col + 3 * n + 1);
+    u64 rl = 0, rh = n;
+    while (rh - rl > 1) {
+      const u64 mid = (rl + rh) / 2;
+      if (loff[mid] <= (long long)k) rl = mid; else rh = mid;
+    }
+    o_vbits[i] = col[4 * n + 2 + k];
+    o_vrow[i] = (long long)(rstart[lo] + rl);
+  }
+}
+
+// One workgroup per EN_UNIT bytes of one MRL1 file, walked like an MRC1 file as
+// the stream t = file offset + 4 (dst % 16 == 4):
+//   t = 4                   "MRL1"
+//   t = 8 + 8 w             word w: n | nb | nv | code | hi[n] | lo[n] | key_off[n + 1] | list_off[n + 1] |
+//                           list_val[nv]
+//   t = 56 + 32 n + 8 nv    key bytes (8 mod 16 for even nv, a 16-byte boundary for odd nv)
+// Words go out as 8-byte stores; key_off and list_off are rebased to the file's
+// first row (off / loff: the n + 1 offsets of the whole sorted table, lval its
+// lval_cap values).  Key bytes: bytes up to the first 16-byte boundary of the
+// destination (only behind the words, at most 8), then as in the MRC1 files.
+__global__ void __launch_bounds__(EN_T) mrl1_encode_kernel(const u64* __restrict__ hi, const u64* __restrict__ lo,
+                                                           const long long* __restrict__ off,
+                                                           const long long* __restrict__ loff,
+                                                           const u64* __restrict__ lval, u64 lval_cap,
+                                                           const u8* __restrict__ blob, u64 blob_cap,
+                                                           const u64* __restrict__ dsts, const u64* __restrict__ rstart,
+                                                           const u64* __restrict__ rows,
+                                                           const u64* __restrict__ unit_start, u32 nfiles, u64 code) {
+  const u64 c = blockIdx.x;
+  u32 flo = 0, fhi = nfiles;
+  while (fhi - flo > 1) {
+    const u32 mid = (flo + fhi) / 2;
+    if (unit_start[mid] <= c) flo = mid; else fhi = mid;
+  }
+  const u32 j = flo;
+  const u64 n = rows[j], a = rstart[j];
+  const u64 o0 = (u64)off[a];
+  const u64 nb = (u64)off[a + n] - o0;
+  const u64 l0 = (u64)loff[a];
+  const u64 nv = (u64)loff[a + n] - l0;
+  const u64 tk = 56 + 32 * n + 8 * nv;  // stream position of the key bytes
+  const u64 tend = tk + nb;             // ... and of the file's end
+  const u64 t0 = (c - unit_start[j]) * EN_UNIT;
+  if (t0 >= tend) return;
+  const u64 t1 = t0 + EN_UNIT < tend ? t0 + EN_UNIT : tend;
+  u8* base = reinterpret_cast<u8*>(dsts[j]) - 4;  // stream position 0: a 16-byte boundary
+  const u32 t = threadIdx.x;
+  if (t0 == 0 && t == 0) *reinterpret_cast<u32*>(base + 4) = 0x314C524Du;  // "MRL1"
+  if (t0 < tk) {
+    const u64 w0 = t0 ? (t0 - 8) / 8 : 0;
+    const u64 w1 = ((t1 < tk ? t1 : tk) - 8) / 8;
+    u64* dw = reinterpret_cast<u64*>(base + 8);
+    for (u64 w = w0 + t; w < w1; w += EN_T) {
+      u64 v;
+      if (w < 4) v = w == 0 ? n : w == 1 ? nb : w == 2 ? nv : code;
+      else if (w < 4 + n) v = hi[a + (w - 4)];
+      else if (w < 4 + 2 * n) v = lo[a + (w - 4 - n)];
+      else if (w < 5 + 3 * n) v = (u64)off[a + (w - 4 - 2 * n)] - o0;
+      else if (w < 6 + 4 * n) v = (u64)loff[a + (w - 5 - 3 * n)] - l0;
+      else {
+        const u64 p = l0 + (w - 6 - 4 * n);
+        v = p < lval_cap ? lval[p] : 0;
+      }
+      dw[w] = v;
+    }
+  }
+  if (t1 > tk) {
+    const u64 b0 = (t0 > tk ? t0 : tk) - tk, b1 = t1 - tk;  // key bytes [b0, b1) of the file
+    u8* d = base + tk + b0;
+    u64 head = (16 - ((tk + b0) & 15)) & 15;  // != 0 only when b0 == 0: every later unit starts on a boundary
+    if (head > b1 - b0) head = b1 - b0;
+    if (t < head) {
+      const u64 p = o0 + b0 + t;
+      d[t] = p < blob_cap ? blob[p] : (u8)0;
+    }
+    put_key_bytes(d + head, blob, blob_cap, o0 + b0 + head, b1 - b0 - head, t);
+  }
+}
+
 }  // namespace mr
 
 using namespace mr;
@@ -547,6 +716,49 @@ int mr_mrc2_encode(const void* hi, const void* lo, const void* off, const void* 
   hipLaunchKernelGGL(mrc2_encode_kernel, dim3((unsigned)nunits), dim3(EN_T), 0, s, (const u64*)hi, (const u64*)lo,
                      (const long long*)off, (const u8*)blob, (u64)blob_cap, p, p + nfiles, p + 2 * nfiles,
                      p + 3 * nfiles, nfiles, *cs);
+  return (int)hipGetLastError();
+}
+
+// out = device i64 [3 * nparts + 3] (mrl1_plan_kernel); counts = order_lists'
+// partition counts, off / loff = its n + 1 sorted key and list offsets
+int mr_mrl1_plan(const void* counts, const void* off, const void* loff, unsigned long long n, unsigned nparts,
+                 void* out, hipStream_t s) {
+  if (nparts == 0 || nparts > (unsigned)PL_T) return -1;
+  hipLaunchKernelGGL(mrl1_plan_kernel, dim3(1), dim3(PL_T), 0, s, (const long long*)counts, (const long long*)off,
+                     (const long long*)loff, (u64)n, nparts, (long long*)out);
+  return (int)hipGetLastError();
+}
+
+unsigned long long mr_mrl1_encode_unit() { return EN_UNIT; }
+
+// plan as for mr_mrc1_encode (a file of n rows, nv values and nb key bytes has
+// 52 + 32 n + 8 nv + nb bytes and ceil((bytes + 4) / unit) units); loff / lval =
+// the sorted table's n + 1 list offsets and its lval_cap values (8-byte words);
+// code = what the files' headers say of them (0 = i64, 1 = f64).
+int mr_mrl1_encode(const void* hi, const void* lo, const void* off, const void* loff, const void* lval,
+                   unsigned long long lval_cap, const void* blob, unsigned long long blob_cap, const void* plan,
+                   unsigned nfiles, unsigned long long nunits, unsigned code, hipStream_t s) {
+  if (nfiles == 0 || nunits == 0) return 0;
+  if (code > 1) return -1;
+  const u64* p = static_cast<const u64*>(plan);
+  hipLaunchKernelGGL(mrl1_encode_kernel, dim3((unsigned)nunits), dim3(EN_T), 0, s, (const u64*)hi, (const u64*)lo,
+                     (const long long*)off, (const long long*)loff, (const u64*)lval, (u64)lval_cap, (const u8*)blob,
+                     (u64)blob_cap, p, p + nfiles, p + 2 * nfiles, p + 3 * nfiles, nfiles, (u64)code);
+  return (int)hipGetLastError();
+}
+
+// meta = device u64 [3 * nfiles + 2]: base[nfiles] | rstart[nfiles + 1] |
+// vstart[nfiles + 1] (prefixes of the files' row and value counts); hi / lo /
+// rep = [nrows], vbits / vrow = [nvals] (nvals may be 0 with rows present)
+int mr_mrl1_decode(const void* buf, const void* meta, unsigned nfiles, unsigned long long nrows,
+                   unsigned long long nvals, void* hi, void* lo, void* rep, void* vbits, void* vrow, hipStream_t s) {
+  if (nrows == 0 || nfiles == 0) return 0;
+  const u64* m = static_cast<const u64*>(meta);
+  const u64 top = nrows > nvals ? nrows : nvals;
+  const u64 g = (top + DC_T - 1) / DC_T;
+  hipLaunchKernelGGL(mrl1_decode_kernel, dim3((unsigned)g), dim3(DC_T), 0, s, (const u8*)buf, m, m + nfiles,
+                     m + 2 * nfiles + 1, nfiles, (u64)nrows, (u64)nvals, (u64*)hi, (u64*)lo, (u64*)rep, (u64*)vbits,
+                     (long long*)vrow);
   return (int)hipGetLastError();
 }
 

@@ -148,6 +148,10 @@ _SIGS = {
     "mr_mrc2_decode": [_p, _p, _u32, _u64, _p, _p, _p, _p, _p],
     "mr_mrc2_encode": [_p, _p, _p, _p, _u64, _p, _p, _u32, _u64, _p],
     "mr_mrc2_encode_unit": [],
+    "mr_mrl1_plan": [_p, _p, _p, _u64, _u32, _p, _p],
+    "mr_mrl1_encode": [_p, _p, _p, _p, _p, _u64, _p, _u64, _p, _u32, _u64, _u32, _p],
+    "mr_mrl1_encode_unit": [],
+    "mr_mrl1_decode": [_p, _p, _u32, _u64, _u64, _p, _p, _p, _p, _p, _p],
     "mr_tail_run_dev": [_p, _p, _p, _p, _p, _p, _u64, _u64, _u32, _p, _p, _p, _u64, _p, _p, _p],
     "mr_wc3_set_dyn": [_i32],
     "mr_agg_set_batch": [_i32],
@@ -155,7 +159,7 @@ _SIGS = {
 }
 _RESTYPE_U64 = {"mr_compact_pack_ws_bytes", "mr_ii_unique_tiles", "mr_text_tiles", "mr_scan_partials_len", "mr_tail_pack_bytes", "mr_tail_ws_layout",
                 "mr_tail_bhist_bytes", "mr_onesweep_tiles", "mr_rec_tie_ws_words", "mr_sdma_d2h_begin",
-                "mr_gather_copy_chunk", "mr_mrc1_encode_unit", "mr_mrc1_encode_units", "mr_mrc2_encode_unit"}
+                "mr_gather_copy_chunk", "mr_mrc1_encode_unit", "mr_mrc1_encode_units", "mr_mrc2_encode_unit", "mr_mrl1_encode_unit"}
 
 MRC2_MAXK = 8  # value columns of an MRC2 file the device codec handles (csrc/hip/ipc.hip; ops/agg.py MAXC)
 MRC2_CODE = {torch.int64: 0, torch.float64: 1, torch.float32: 2}  # runtime/codec.py _DT_CODE

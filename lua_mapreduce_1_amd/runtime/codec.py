@@ -10,7 +10,11 @@ replace it:
   (host plane: arbitrary Python keys/values from user map/reduce functions).
 * ``MRC1`` — columnar device format: u64 key words (hi, lo), int64 values and
   the key bytes (offsets + blob), straight from HBM buffers (device plane);
-  ``MRC2`` the same with K typed value columns (the general plane's folds).
+  ``MRC2`` the same with K typed value columns (the general plane's folds);
+  ``MRL1`` keys with a value LIST each (CSR: ``list_off`` / ``list_val``, 8-byte
+  i64 or f64 words), the general plane's list maps under ``hbm`` storage —
+  :func:`decode_records` reads it as the ``(key, [values])`` records an
+  ``MRK1`` file of the same partition holds.
 """
 from __future__ import annotations
 
@@ -58,6 +62,8 @@ def decode_records(data: bytes) -> Iterator[tuple]:
         return iter_columnar(decode_columnar(data))
     if data[:4] == MAGIC_COL2:
         return iter_columnar(decode_columns(data))
+    if data[:4] == MAGIC_LIST:
+        return iter_columnar(decode_lists(data))
     if data[:4] != MAGIC_REC:
         raise ValueError("unknown intermediate file format")
     up = msgpack.Unpacker(use_list=False, raw=False, strict_map_key=False, unicode_errors="surrogateescape")
@@ -128,6 +134,65 @@ def decode_columns(data: bytes) -> dict:
         p += dt.itemsize * n
     out["cols"] = cols
     out["key_blob"] = np.frombuffer(data, dtype=np.uint8, count=nb, offset=p)
+    return out
+
+
+# ---------------------------------------------------------------------------
+MAGIC_LIST = b"MRL1"
+_LIST_DT = {0: np.dtype(np.int64), 1: np.dtype(np.float64)}  # code: how list_val's 8-byte words are read
+
+
+def encode_lists(hi: np.ndarray, lo: np.ndarray, key_off: np.ndarray, key_blob: np.ndarray, list_off: np.ndarray,
+                 list_val: np.ndarray, code: int) -> bytes:
+    """``MRL1``: keys with one value list each (a key's list may be empty), the
+    general plane's list maps (parallel/generic.py ``order_lists``, scalar
+    values).  All integers little-endian::
+
+        "MRL1" | n u64 | nb u64 | nv u64 | code u64 (0 = i64, 1 = f64)
+        hi[n] u64 | lo[n] u64 | key_off[n+1] i64 (from 0) | list_off[n+1] i64 (from 0, list_off[n] = nv)
+        list_val[nv] (8-byte words: the stored bits) | key bytes [nb]
+
+    ``52 + 32 n + 8 nv + nb`` bytes.  ``list_val``: int64 or float64 values (or
+    their bits as uint64); only their bits are written, ``code`` says how a
+    reader views them.  This is the specification of the device codec
+    (csrc/hip/ipc.hip ``mr_mrl1_encode`` / ``mr_mrl1_decode``)."""
+    n, nb = int(hi.size), int(key_blob.size)
+    code = int(code)
+    if code not in _LIST_DT:
+        raise ValueError(f"MRL1: value code {code} (0 = i64, 1 = f64)")
+    key_off = np.ascontiguousarray(key_off, np.int64)
+    list_off = np.ascontiguousarray(list_off, np.int64)
+    lv = np.ascontiguousarray(list_val)
+    if lv.dtype.itemsize != 8:
+        raise ValueError(f"MRL1: values of {lv.dtype} are not 8-byte words")
+    nv = int(lv.size)
+    if key_off.size != n + 1 or list_off.size != n + 1 or int(lo.size) != n:
+        raise ValueError("MRL1: hi, lo, key_off and list_off do not describe the same keys")
+    if int(key_off[0]) != 0 or int(key_off[n]) != nb or int(list_off[0]) != 0 or int(list_off[n]) != nv:
+        raise ValueError("MRL1: key_off / list_off do not start at 0 or do not end at the byte / value count")
+    return b"".join([MAGIC_LIST, struct.pack("<QQQQ", n, nb, nv, code), np.ascontiguousarray(hi, np.uint64).tobytes(),
+                     np.ascontiguousarray(lo, np.uint64).tobytes(), key_off.tobytes(), list_off.tobytes(),
+                     lv.view(np.uint64).tobytes(), np.ascontiguousarray(key_blob, np.uint8).tobytes()])
+
+
+def decode_lists(data: bytes) -> dict:
+    """An ``MRL1`` file's columns: hi, lo, key_off, key_blob, list_off,
+    list_val (int64, or float64 viewed from the bits) and ``code``."""
+    if data[:4] != MAGIC_LIST:
+        raise ValueError("not an MRL1 file")
+    if len(data) < 36:
+        raise ValueError("MRL1: truncated header")
+    n, nb, nv, code = struct.unpack("<QQQQ", data[4:36])
+    if code not in _LIST_DT:
+        raise ValueError(f"MRL1: value code {code} (0 = i64, 1 = f64)")
+    if 52 + 32 * n + 8 * nv + nb != len(data):
+        raise ValueError(f"MRL1: a file of {len(data)} bytes cannot hold {n} keys, {nv} values and {nb} key bytes")
+    p = 36
+    out = {"code": int(code)}
+    for name, dt, cnt in (("hi", np.uint64, n), ("lo", np.uint64, n), ("key_off", np.int64, n + 1),
+                          ("list_off", np.int64, n + 1), ("list_val", _LIST_DT[code], nv), ("key_blob", np.uint8, nb)):
+        out[name] = np.frombuffer(data, dtype=dt, count=cnt, offset=p)
+        p += np.dtype(dt).itemsize * cnt
     return out
 
 

@@ -940,6 +940,99 @@ def fold_columns_to_arena(out: dict, nparts: int, names_for, gen=None):
                           mrc2=[{"rows": int(r), "nb": int(b), "codes": codes} for r, b in zip(rows, nbs)])
 
 
+def mrl1_file_plan(plan: np.ndarray, n: int, nparts: int, blob_cap: int, val_cap: int):
+    """What the downloaded plan of ``mr_mrl1_plan`` (int64 [3 * nparts + 3]:
+    rows | key bytes | values | off[n] | list_off[n] | sum of the rows) allows:
+    ``None`` unless the counts account for exactly the n rows, ``off[n]`` key
+    bytes within the blob (``blob_cap``) and ``list_off[n]`` values within
+    ``list_val`` (``val_cap``) — else ``(partitions, row starts, rows, key
+    bytes, values, file sizes)`` of the non-empty partitions' MRL1 files
+    (int64 arrays; a file: 52 + 32 n + 8 nv + nb bytes)."""
+    plan = np.asarray(plan, np.int64)
+    rows, nbs, nvs = plan[:nparts], plan[nparts:2 * nparts], plan[2 * nparts:3 * nparts]
+    total_nb, total_nv, total_rows = (int(x) for x in plan[3 * nparts:3 * nparts + 3])
+    if total_rows != n or (rows < 0).any() or (nbs < 0).any() or (nvs < 0).any():
+        return None
+    if not 0 <= total_nb <= blob_cap or int(nbs.sum()) != total_nb:
+        return None
+    if not 0 <= total_nv <= val_cap or int(nvs.sum()) != total_nv:
+        return None
+    starts = np.zeros(nparts, np.int64)
+    np.cumsum(rows[:-1], out=starts[1:])
+    parts = np.flatnonzero(rows > 0)
+    r, b, v = rows[parts], nbs[parts], nvs[parts]
+    return parts, starts[parts], r, b, v, 52 + 32 * r + 8 * v + b
+
+
+def lists_to_arena(out: dict, nparts: int, names_for, code: int, gen=None):
+    """A list map's partition files written on the device (``hbm`` storage),
+    the twin of :func:`fold_columns_to_arena`.  ``out``: the sorted device
+    columns of ``parallel/generic.py::order_lists`` (scalar values:
+    ``list_val``) in exact (partition, key) order; ``code``: how the values'
+    bits are read (0 = i64, 1 = f64).  ONE plan launch (mr_mrl1_plan over the
+    partition counts, key offsets and list offsets) and ONE download of
+    ``8 * (3 * nparts + 3)`` bytes size the files, places are reserved in this
+    process's arena, ONE encode launch (mr_mrl1_encode, csrc/hip/ipc.hip)
+    writes every non-empty partition's MRL1 file into its place — byte for
+    byte what ``codec.encode_lists`` makes of ``host_partitions``' slices —
+    and the files' descriptors come back: ``[(names_for(p), descriptor)]`` in
+    partition order.  ``None`` when this path does not apply (no device arena,
+    more than 256 partitions, an inexact order, tuple or byte-string values
+    (``list_cols``), no key) or the plan must not be trusted
+    (:func:`mrl1_file_plan`); nothing is reserved then, and the caller writes
+    the same ``out`` on the host.  Callers hold PLANE_LOCK."""
+    from ..ops import _hip
+    from . import hbm_store
+    if "list_cols" in out or "list_val" not in out or int(code) not in (0, 1):
+        return None
+    hi, lo, off, blob, loff, lval = (out[k] for k in ("hi", "lo", "key_off", "key_blob", "list_off", "list_val"))
+    n = int(hi.numel())
+    if not (hi.is_cuda and out.get("exact") and 0 < nparts <= 256 and n > 0 and hi.device == default_device()
+            and hi.dtype == lo.dtype == off.dtype == loff.dtype == lval.dtype == torch.int64
+            and off.numel() == n + 1 and loff.numel() == n + 1 and lval.dim() == 1):
+        return None
+    d = hi.device
+    hi, lo, off, loff, lval, blob = (t.contiguous() for t in (hi, lo, off, loff, lval, blob))
+    aw = _arena_ws(d)
+    if "lplan" not in aw:
+        aw["lplan"] = torch.zeros(3 * 256 + 3, dtype=torch.int64, device=d)
+    s = _hip.stream(d)
+    counts = out["counts"].to(torch.int64).contiguous()
+    if counts.numel() != nparts:
+        return None
+    _hip.call("mr_mrl1_plan", _hip.ptr(counts), _hip.ptr(off), _hip.ptr(loff), n, nparts, _hip.ptr(aw["lplan"]), s)
+    plan_words = 3 * nparts + 3
+    got = mrl1_file_plan(ops.host_read(aw["lplan"][:plan_words]), n, nparts, int(blob.numel()), int(lval.numel()))
+    if got is None:
+        return None
+    parts, starts, rows, nbs, nvs, sizes = got
+    st = hbm_store.store()
+    if not st.on_gpu():  # (before anything is reserved: a place given out is arena space spent)
+        return None
+    unit = _ENC_UNIT.get("unitl")
+    if unit is None:
+        unit = _ENC_UNIT["unitl"] = int(_hip.lib().mr_mrl1_encode_unit())
+    units = (sizes + 4 + unit - 1) // unit  # (a file's stream starts 4 bytes before it)
+    nf = int(sizes.size)
+    with st.writer():  # (held from the reservation to the publication, as in finalize_table_to_arena)
+        places = st.reserve_many(sizes.tolist(), gen)
+        tab = aw["htab"].numpy()
+        tab[:nf] = np.array([pl.ptr for pl in places], np.uint64).view(np.int64)
+        tab[nf:2 * nf] = starts
+        tab[2 * nf:3 * nf] = rows
+        tab[3 * nf] = 0
+        np.cumsum(units[:-1], out=tab[3 * nf + 1:4 * nf])
+        _hip.call("mr_memcpy_async", _hip.ptr(aw["tab"]), _hip.ptr(aw["htab"]), 8 * 4 * nf, 1, s)
+        _hip.call("mr_mrl1_encode", _hip.ptr(hi), _hip.ptr(lo), _hip.ptr(off), _hip.ptr(loff), _hip.ptr(lval),
+                  int(lval.numel()), _hip.ptr(blob), int(blob.numel()), _hip.ptr(aw["tab"]), nf, int(units.sum()),
+                  int(code), s)
+        _hip.wait_stream(d)
+        return st.publish([names_for(int(p)) for p in parts], places, sizes.tolist(), [-1] * nf, [-1] * nf,
+                          plan_bytes=8 * plan_words,
+                          mrl1=[{"rows": int(r), "nb": int(b), "nv": int(v), "code": int(code)}
+                                for r, b, v in zip(rows, nbs, nvs)])
+
+
 def _unpack_fused(pend: dict):
     """(val int64[n], off int32[n+1], counts int64[nparts], bad) views of the packed download."""
     n, nparts = pend["n"], pend["nparts"]

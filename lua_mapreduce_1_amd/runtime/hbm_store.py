@@ -21,14 +21,17 @@ for the workers of ONE node:
 * the write side depends on who wrote the file.  A device map on a GPU
   worker with ``MR_HBM_DEVICE_WRITE`` on — a fold map
   (``job._run_device_map_locked``, MRC1 files) or a typed-fold map
-  (``job._run_generic_map`` with a column spec, MRC2 files) — reserves places
+  (``job._run_generic_map`` with a column spec, MRC2 files) or a list map
+  (the same job without ``device_reduce`` or with a concat op, scalar i64 /
+  f64 values: MRL1 files, every key with its value list) — reserves places
   in the arena (:meth:`HBMStore.reserve_many`), has ONE encode launch write
   its files there, and publishes them (:meth:`HBMStore.publish`): only a plan
-  of ``8 * (2 * nparts + 4)`` bytes comes to the host, no byte of the files
-  moves either way.  Every other writer — the general plane's record files
-  (value lists), a host map, a fold map whose tail raised a flag, a typed
-  fold the device codec does not take (more than 256 partitions, an inexact
-  key order) — hands host ``bytes`` to :meth:`HBMStore.put_many`, which
+  of ``8 * (2 * nparts + 4)`` bytes (a list map: ``8 * (3 * nparts + 3)``)
+  comes to the host, no byte of the files moves either way.  Every other
+  writer — a list map with tuple or byte-string values (MRK1 records), a host
+  map, a fold map whose tail raised a flag, a typed fold or list map the
+  device codec does not take (more than 256 partitions, an inexact key
+  order) — hands host ``bytes`` to :meth:`HBMStore.put_many`, which
   stages them through pinned memory and uploads them
   (``stats["staged_bytes"]`` counts these);
 * reduce results go to the coordinator like every storage's
@@ -42,8 +45,11 @@ pull buffer); a worker without a GPU cannot read a file that lives in a
 GPU's memory and fails that job with an error that says so.  Only a fold
 whose files are all columnar (``rows >= 0`` in every descriptor: MRC1; an
 ``mrc2`` entry in every descriptor: MRC2, whose ``rows`` stays -1) is decoded
-on the device from the pulled buffer; record files of a host map are read
-to the host and merged there.
+on the device from the pulled buffer, and so is a list reduce whose files all
+carry an ``mrl1`` entry with one value code (MRL1: decoded by ONE launch, the
+rows merged per key on the device, ``job._reduce_list_rows``); record files of
+a host map are read to the host and merged there — MRL1 files of the same
+partition with them (``codec.decode_records`` reads both).
 
 Lifetime: an owner keeps its chunks until its worker starts the map phase of
 a later iteration or finishes the task (every reduce of the iteration has then
@@ -85,6 +91,16 @@ def mrc2_header(data) -> dict | None:
     if not 1 <= k <= 8:
         return None
     return {"rows": n, "nb": nb, "codes": list(bytes(data[28:28 + k]))}
+
+
+def mrl1_header(data) -> dict | None:
+    """``{"rows", "nb", "nv", "code"}`` an MRL1 file's header declares
+    (runtime/codec.py ``encode_lists``), as its descriptor carries them; None
+    for any other file."""
+    if len(data) < 36 or bytes(data[:4]) != b"MRL1":
+        return None
+    n, nb, nv, code = struct.unpack_from("<qqqq", data, 4)
+    return {"rows": n, "nb": nb, "nv": nv, "code": code}
 
 
 def _shm_dir() -> str:
@@ -209,7 +225,7 @@ class HBMStore:
                 rows = nb = -1
                 if len(data) >= 20 and data[:4] == b"MRC1":
                     rows, nb = struct.unpack_from("<qq", data, 4)
-                out.append((name, self._descriptor(c, off, len(data), rows, nb, mrc2_header(data))))
+                out.append((name, self._descriptor(c, off, len(data), rows, nb, mrc2_header(data), mrl1_header(data))))
                 self.stats["staged_bytes"] += len(data)
             return out
 
@@ -219,11 +235,14 @@ class HBMStore:
         if gen is not None:
             self._gen = gen
 
-    def _descriptor(self, c: _Chunk, off: int, size: int, rows: int, nb: int, mrc2: dict | None = None) -> bytes:
+    def _descriptor(self, c: _Chunk, off: int, size: int, rows: int, nb: int, mrc2: dict | None = None,
+                    mrl1: dict | None = None) -> bytes:
         d = {"host": self.host, "pid": self.pid, "dev": self._device.index if self._gpu() else -1,
              "c": c.cid, "h": c.handle.hex(), "off": off, "len": size, "rows": rows, "nb": nb}
         if mrc2 is not None:  # an MRC2 file's own counts and dtype codes (rows / nb above stay -1: not an MRC1 file)
             d["mrc2"] = {"rows": int(mrc2["rows"]), "nb": int(mrc2["nb"]), "codes": [int(x) for x in mrc2["codes"]]}
+        if mrl1 is not None:  # an MRL1 file's own counts and value code (rows / nb above stay -1 here too)
+            d["mrl1"] = {k: int(mrl1[k]) for k in ("rows", "nb", "nv", "code")}
         self.stats["puts"] += 1
         self.stats["put_bytes"] += size
         return MAGIC + json.dumps(d, separators=(",", ":")).encode()
@@ -256,24 +275,28 @@ class HBMStore:
             return [Place(c, off, int(n)) for n in sizes for c, off in (self._place(int(n)),)]
 
     def publish(self, names: list[str], places: list[Place], sizes: list[int], rows: list[int], nbs: list[int],
-                plan_bytes: int = 0, mrc2: list | None = None) -> list[tuple[str, bytes]]:
+                plan_bytes: int = 0, mrc2: list | None = None, mrl1: list | None = None) -> list[tuple[str, bytes]]:
         """(name, descriptor) pairs of files written into reserved places —
         what :meth:`put_many` returns for the same bytes.  ``rows`` / ``nbs``:
         the MRC1 header counts (-1 for any other file).  ``mrc2``: per file
         ``{"rows", "nb", "codes"}`` of an MRC2 file's header (:func:`mrc2_header`;
-        None for any other file).  The writer has finished (its stream is
+        None for any other file); ``mrl1``: per file ``{"rows", "nb", "nv",
+        "code"}`` of an MRL1 file's header (:func:`mrl1_header`; None for any
+        other file).  The writer has finished (its stream is
         synchronised) before it publishes.  ``plan_bytes``: what it downloaded
         to size the files."""
         if mrc2 is None:
             mrc2 = [None] * len(names)
-        if not (len(names) == len(places) == len(sizes) == len(rows) == len(nbs) == len(mrc2)):
+        if mrl1 is None:
+            mrl1 = [None] * len(names)
+        if not (len(names) == len(places) == len(sizes) == len(rows) == len(nbs) == len(mrc2) == len(mrl1)):
             raise ValueError("hbm storage: publish() lists differ in length")
         with self._lock:
             out = []
-            for name, pl, size, r, nb, m2 in zip(names, places, sizes, rows, nbs, mrc2):
+            for name, pl, size, r, nb, m2, ml in zip(names, places, sizes, rows, nbs, mrc2, mrl1):
                 if int(size) != pl.size or pl.chunk not in self._chunks:
                     raise RuntimeError(f"hbm storage: {name} does not fit its reserved place (or the arena was released)")
-                out.append((name, self._descriptor(pl.chunk, pl.off, pl.size, int(r), int(nb), m2)))
+                out.append((name, self._descriptor(pl.chunk, pl.off, pl.size, int(r), int(nb), m2, ml)))
                 self.stats["dev_puts"] += 1
                 self.stats["dev_put_bytes"] += pl.size
             self.stats["plan_bytes"] += int(plan_bytes)

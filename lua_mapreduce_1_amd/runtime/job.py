@@ -72,6 +72,8 @@ def reset_cache() -> None:
 
 FOLD_OPS = ("sum", "min", "max", "count")
 LIST_OPS = ("concat", "concat_unique")
+_MRL1_CODE = {"i64": 0, "f64": 1}  # value code of an MRL1 file (codec.encode_lists) by scalar value dtype
+_MRL1_DTYPE = {v: k for k, v in _MRL1_CODE.items()}
 
 
 def device_kind(task_tbl: dict | None, mod_map, mod_red=None) -> str | None:
@@ -83,9 +85,10 @@ def device_kind(task_tbl: dict | None, mod_map, mod_red=None) -> str | None:
     * ``"cols"`` — a typed column spec (ops/agg.py), ``MRC2`` outputs merged
       by the device reduce;
     * ``"list"`` — no device_reduce (or a concat op): values grouped per key
-      on the device, written as ``(key, [values])`` records that the reduce
-      job hands to the module's own reducefn (job.lua:264-284) — never a
-      fold the user did not declare;
+      on the device, written as ``(key, [values])`` records (``MRK1``, or
+      columnar ``MRL1`` files under ``hbm`` storage) that the reduce job
+      hands to the module's own reducefn (job.lua:264-284) — never a fold
+      the user did not declare;
     * ``"identity"`` (the record plane) runs in SPMD mode only: host mapfn."""
     want = (task_tbl or {}).get("device", "auto")
     if want in (False, "never", "host"):
@@ -269,8 +272,8 @@ class job:  # noqa: N801
 
     def _run_generic_map(self, pmod, rmod, kind: str):
         """General device map of one job (parallel/generic.py): typed folds
-        (``MRC2`` partition files) or per-key value lists (``MRK1`` records
-        for the host reducefn)."""
+        (``MRC2`` partition files) or per-key value lists (``MRK1`` records;
+        ``MRL1`` files written on the device under ``hbm`` storage)."""
         from ..ops import agg as A
         from ..parallel import generic as G
         clock1 = _time.process_time()
@@ -327,6 +330,19 @@ class job:  # noqa: N801
         else:
             space = gm.table.cap if gm.table.is_cuda else max(1, n)
             out = G.order_lists(*gm.table.postings(), src, nparts, pmod, spec == "concat_unique", dtype, space)
+            if (self.storage == "hbm" and _DUMP is None and config.TUNABLES.hbm_device_write and d.type == "cuda"
+                    and dtype.scalar and dtype.dtype in _MRL1_CODE and out["exact"] and 0 < nparts <= 256
+                    and "list_val" in out and out["hi"].numel() > 0):
+                # the MRL1 partition files (every key with its value list) are written on the device, straight
+                # into this worker's arena; None: the plan was not trusted -> the host path below (MRK1 records)
+                descs = dev.lists_to_arena(out, nparts, lambda p: f"{self.path}/{self.results_ns}.P{p}.M{map_key}",
+                                           _MRL1_CODE[dtype.dtype], gen=self._gen())
+                if descs is not None:
+                    index = [(INDEX_PREFIX + name + INDEX_SEP + host, b"") for name, _ in descs]
+                    self.cnn.gridfs().store_many(descs + index)
+                    elapsed = _time.process_time() - clock1
+                    self.mark_as_written(elapsed)
+                    return elapsed
         parts = G.host_partitions(out, nparts, dtype)
         outputs, index = [], []
         for p, cols in sorted(parts.items()):
@@ -447,8 +463,20 @@ class job:  # noqa: N801
                 magic = codec.MAGIC_COL2 if cols_op else codec.MAGIC_COL
                 if pulled is None and not all(b[:4] == magic for b in blobs):
                     blobs = None
+            lists_pulled = None
+            if not (dev_op in FOLD_OPS or cols_op) and filenames and self.storage == "hbm" \
+                    and dev.default_device().type == "cuda":
+                # a list reduce whose map files are all MRL1 files of one value code stays on the device
+                from . import hbm_store
+                descs = [x or b"" for x in self.cnn.gridfs().get_many(filenames)]
+                if all(hbm_store.is_descriptor(x) for x in descs) and _hbm_route_lists(descs, True) == "pull":
+                    lists_pulled = descs
             b = rbuilder()
-            if blobs is not None:
+            if lists_pulled is not None:
+                with dev.PLANE_LOCK:
+                    recs = _device_reduce_lists_hbm(lists_pulled, self.module, g, aci, dev_reducefn is not None)
+                b.append(codec.encode_records(recs))
+            elif blobs is not None:
                 with dev.PLANE_LOCK:
                     if pulled is not None:
                         out = _device_reduce_cols_hbm(pulled, dev_op) if cols_op else _device_reduce_hbm(pulled, dev_op)
@@ -791,6 +819,146 @@ def _fold_cols(phys, hi, lo, rep, vals: list, src) -> bytes:
                                     [np.zeros(0, c.dtype) for c in G._np_cols(out)], np.zeros(1, np.int64),
                                     np.zeros(0, np.uint8))
     return codec.encode_columns(part["hi"], part["lo"], part["cols"], part["key_off"], part["key_blob"])
+
+
+def _hbm_route_lists(descs: list[bytes], on_gpu: bool) -> str:
+    """:func:`_hbm_route` for a list reduce (no ``device_reduce``, or a concat
+    op): ``"pull"`` (gather copy + MRL1 decode + the per-key merge on the
+    device) only on a GPU when EVERY descriptor carries an MRL1 file's counts
+    (``mrl1``) and all of them the same value code.  Otherwise ``"read"``: the
+    host merge reads the files, MRL1 and MRK1 side by side
+    (``codec.decode_records``)."""
+    from . import hbm_store
+    if not on_gpu or not descs:
+        return "read"
+    heads = [hbm_store.HBMStore.parse(x).get("mrl1") for x in descs]
+    if all(isinstance(h, dict) for h in heads) and len({h.get("code") for h in heads}) == 1 \
+            and heads[0].get("code") in _MRL1_DTYPE:
+        return "pull"
+    return "read"
+
+
+def _check_mrl1_layout(size: int, bases, rows, lens, key_bytes, nvals) -> None:
+    """:func:`_check_mrc1_layout` for MRL1 files: the decode kernel reads
+    ``rows[j]`` rows of hi, lo, key_off and list_off and ``nvals[j]`` values
+    behind file j's 36-byte header, and writes as many rows and values, without
+    a bound of its own.  ValueError for a negative count, values without a row
+    to own them, a length that is not ``52 + 32 n + 8 nv + nb``, or a file that
+    does not lie inside the buffer at 4 mod 8."""
+    if not (len(bases) == len(rows) == len(lens) == len(key_bytes) == len(nvals)):
+        raise ValueError("MRL1 decode: bases, rows, lens, key_bytes and nvals differ in length")
+    for j, (b, n, ln, nb, nv) in enumerate(zip(bases, rows, lens, key_bytes, nvals)):
+        b, n, ln, nb, nv = int(b), int(n), int(ln), int(nb), int(nv)
+        if n < 0 or nb < 0 or nv < 0:
+            raise ValueError(f"MRL1 decode: file {j} has row count {n}, key bytes {nb}, values {nv} (not an MRL1 file)")
+        if n == 0 and nv > 0:
+            raise ValueError(f"MRL1 decode: file {j} has {nv} values and no row")
+        if 52 + 32 * n + 8 * nv + nb != ln:
+            raise ValueError(f"MRL1 decode: file {j} of {ln} bytes cannot hold {n} rows, {nv} values and {nb} key bytes")
+        if b < 0 or b % 8 != 4 or b + ln > size:
+            raise ValueError(f"MRL1 decode: file {j} at {b} (+{ln}) is misplaced in a buffer of {size} bytes")
+
+
+def _decode_list_files(buf: torch.Tensor, bases: list[int], rows: list[int], lens: list[int], key_bytes: list[int],
+                       nvals: list[int]):
+    """MRL1 files at ``bases`` of one device buffer -> (hi, lo, rep [rows],
+    value bits, value row [values]), ONE launch (csrc/hip/ipc.hip); rep words
+    index ``buf``, a value's row is its global row index.  Everything the
+    kernel will index is checked first (:func:`_check_mrl1_layout`), before
+    anything is allocated or launched."""
+    _check_mrl1_layout(buf.numel(), bases, rows, lens, key_bytes, nvals)
+    from ..ops import _hip
+    d = buf.device
+    rstart = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum(rows, out=rstart[1:])
+    vstart = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum(nvals, out=vstart[1:])
+    n, nv = int(rstart[-1]), int(vstart[-1])
+    meta = torch.from_numpy(np.concatenate([np.asarray(bases, np.int64), rstart, vstart])).to(d)
+    keys = torch.empty((3, max(n, 1)), dtype=torch.int64, device=d)
+    hi, lo, rep = (keys[i, :n] for i in range(3))
+    vals = torch.empty((2, max(nv, 1)), dtype=torch.int64, device=d)
+    vbits, vrow = vals[0, :nv], vals[1, :nv]
+    if n:
+        _hip.call("mr_mrl1_decode", _hip.ptr(buf), _hip.ptr(meta), len(rows), n, nv, _hip.ptr(hi), _hip.ptr(lo),
+                  _hip.ptr(rep), _hip.ptr(vbits), _hip.ptr(vrow), _hip.stream(d))
+    return hi, lo, rep, vbits, vrow
+
+
+def _reduce_list_rows(hi, lo, rep, src, vbits, vrow, dtype) -> dict:
+    """The rows of a partition's list files (keys with rep words into ``src``;
+    value i has bits ``vbits[i]`` and belongs to row ``vrow[i]``; rows and
+    values in the order of the files, then in file order) merged per key, on
+    the rows' device: ``order_lists``' result for one partition — every key
+    once (exact equality: long keys verified against their bytes), in exact
+    bytewise order, its values concatenated in input order (the tie rule of
+    ``utils.merge_iterator``), a key whose lists are all empty kept with an
+    empty list.  The receive side of the SPMD shuffle does the same: a
+    list-mode table gives every row its key's slot (in row order), the values
+    take their rows' slots."""
+    from ..ops import agg as A
+    from ..parallel import generic as G
+    d = hi.device
+    n = int(hi.numel())
+    cap = max(1024, 4 * n)
+    while True:
+        tab = A.AggTable(cap, d, None, "i64")
+        tab.src = src
+        tab.insert(n, [], hi=hi, lo=lo, rep=rep)
+        m, ovf = tab.stats()
+        if not ovf:
+            break
+        cap *= 4
+    slot, khi, klo, krep, kslot, _ = tab.postings()
+    pslot = kslot[vrow] if n else kslot[:0]
+    space = tab.cap if tab.is_cuda else max(1, int(khi.numel()))
+    return G.order_lists(slot, khi, klo, krep, pslot, vbits, src, 1, None, False, dtype, space)
+
+
+def _list_records(out: dict, rmod, reducefn, aci: bool, batched: bool, dtype: str) -> list:
+    """A list reduce's merged partition (:func:`_reduce_list_rows`) -> the
+    result records, as the host route makes them of the merged lists: through
+    the module's batched ``device_reducefn`` straight over the device CSR
+    (``batched``), else ONE download and the module's ``reducefn`` per key
+    (skipped for a singleton list under the three ACI flags, job.lua:264-274)."""
+    from ..parallel import generic as G
+    from ..parallel import reducers as RD
+    if int(out["hi"].numel()) == 0:
+        return []
+    if batched:
+        red = RD.ListReducers(rmod, dtype)
+        if red.device_reducefn is not None:
+            keys = RD.KeyBatch(out["hi"], out["lo"], key_off=out["key_off"], key_blob=out["key_blob"])
+            res = red.reduce_device(keys, out["list_off"], out["list_val"])  # (the values' int64 bits)
+            res.update(hi=out["hi"], lo=out["lo"], key_off=out["key_off"], key_blob=out["key_blob"],
+                       exact=bool(out.get("exact", False)), counts=out["counts"])
+            part = G.host_partitions(res, 1, dtype).get(0)
+            return [(k, list(v)) for k, v in codec.iter_columnar(part)]
+    recs = []
+    for k, v in codec.iter_columnar(G.host_partitions(out, 1, dtype).get(0)):
+        if not aci or len(v) > 1:
+            o: list = []
+            reducefn(k, v, o.append)
+            v = [tuple_(x) for x in o]
+        recs.append((k, v))
+    return recs
+
+
+def _device_reduce_lists_hbm(descs: list[bytes], rmod, reducefn, aci: bool, batched: bool) -> list:
+    """``hbm`` storage, list reduce: the partition's MRL1 files are pulled from
+    the map workers' device arenas (peer to peer, one launch), decoded (one
+    launch) and merged per key on the device — no host copy of the
+    intermediate data, no per-value Python before the reducer."""
+    from . import hbm_store
+    buf, bases, ds = hbm_store.store().pull_device(descs, dev.default_device())
+    ml = [x.get("mrl1") or {} for x in ds]
+    codes = {m.get("code") for m in ml}
+    if len(codes) != 1 or next(iter(codes)) not in _MRL1_DTYPE:
+        raise ValueError(f"MRL1 decode: the files have value codes {sorted(map(str, codes))} (one of {sorted(_MRL1_DTYPE)})")
+    dtype = _MRL1_DTYPE[next(iter(codes))]
+    hi, lo, rep, vbits, vrow = _decode_list_files(buf, bases, [m.get("rows", -1) for m in ml], [x["len"] for x in ds],
+                                                  [m.get("nb", -1) for m in ml], [m.get("nv", -1) for m in ml])
+    return _list_records(_reduce_list_rows(hi, lo, rep, buf, vbits, vrow, dtype), rmod, reducefn, aci, batched, dtype)
 
 
 def _device_reduce_lists(merged: list, rmod) -> list | None:

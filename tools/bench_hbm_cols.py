@@ -11,7 +11,14 @@ answer is checked against the generator's own group-by.  One JSON line per
 run (server time, ``Map sum(cpu_time)``, ``Reduce sum(cpu_time)`` of the
 server's stats block) and one summary line.
 
-    python tools/bench_hbm_cols.py [--lines 2000000] [--workers 1] [--repeat 3] [--storage hbm]
+``--job latency`` runs examples/LatencyStats instead (percentiles per endpoint
+through ``device_reducefn``, no combiner: a list map whose MRL1 files hold
+every value): with the knob on its map files are written by one encode launch
+and its reduce jobs merge them on the device, with it off they are MRK1
+records packed, merged and re-encoded on the host.  The log comes from the
+example's ``make_log`` (seed 11), the answer is checked against its ``naive``.
+
+    python tools/bench_hbm_cols.py [--job scores] [--lines 2000000] [--workers 1] [--repeat 3] [--storage hbm]
 """
 from __future__ import annotations
 
@@ -28,17 +35,18 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-SS = "lua_mapreduce_1_amd.examples.ScoreStats"
+JOBS = {"scores": "lua_mapreduce_1_amd.examples.ScoreStats", "latency": "lua_mapreduce_1_amd.examples.LatencyStats"}
 
 
-def serve(conn: str, db: str, storage: str, files: list[str], out: str) -> int:
-    """The server process: one ScoreStats task over ``files``; its stats
+def serve(conn: str, db: str, storage: str, files: list[str], out: str, job: str = "scores") -> int:
+    """The server process: one task of the job's module over ``files``; its stats
     block and the final answer go to ``out`` (msgpack)."""
     import importlib
 
     import msgpack
     from lua_mapreduce_1_amd import server
     from lua_mapreduce_1_amd.cli.execute_server import ensure_coordinator
+    SS = JOBS[job]
     s = server.new(ensure_coordinator(conn), db)
     s.poll_sleep = 0.01
     s.quiet = True
@@ -58,7 +66,8 @@ def run_once(a, rep: int, knob: bool, files: list[str], tmp: str) -> dict:
                MR_HBM_DEVICE_WRITE="1" if knob else "0")
     flist = os.path.join(tmp, "files.json")
     slog = open(os.path.join(tmp, f"server.r{rep}.txt"), "w")
-    server = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--serve", conn, db, a.storage, flist, out],
+    server = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--serve", conn, db, a.storage, flist, out,
+                               a.job],
                               stdout=subprocess.DEVNULL, stderr=slog, env=env)
     time.sleep(1.0)
     wlogs = [open(os.path.join(tmp, f"worker{i}.r{rep}.txt"), "w") for i in range(a.workers)]
@@ -101,9 +110,12 @@ def main() -> int:
     if len(sys.argv) > 1 and sys.argv[1] == "--serve":
         conn, db, storage, flist, out = sys.argv[2:7]
         with open(flist) as f:
-            return serve(conn, db, storage, json.load(f), out)
+            return serve(conn, db, storage, json.load(f), out, *sys.argv[7:8])
     ap = argparse.ArgumentParser()
+    ap.add_argument("--job", choices=sorted(JOBS), default="scores")
     ap.add_argument("--lines", type=int, default=2_000_000)
+    ap.add_argument("--endpoints", type=int, default=5000, help="--job latency: distinct keys")
+    ap.add_argument("--splits", type=int, default=64, help="--job latency: split files (map jobs)")
     ap.add_argument("--workers", type=int, default=1)
     ap.add_argument("--repeat", type=int, default=3, help="validated runs per setting (off, on, off, on, ...)")
     ap.add_argument("--storage", default="hbm")
@@ -112,8 +124,14 @@ def main() -> int:
     a = ap.parse_args()
     from lua_mapreduce_1_amd.utils import corpus
     t0 = time.time()
-    splits, truth = corpus.score_csv(seed=11, lines=a.lines, vocab_size=300_000, split_lines=max(1, a.lines // 197),
-                                     return_truth=True)
+    if a.job == "latency":
+        import importlib
+        ls = importlib.import_module(JOBS["latency"])
+        splits = ls.make_log(seed=11, lines=a.lines, endpoints=a.endpoints, nsplits=a.splits)
+        truth = ls.naive(splits)
+    else:
+        splits, truth = corpus.score_csv(seed=11, lines=a.lines, vocab_size=300_000,
+                                         split_lines=max(1, a.lines // 197), return_truth=True)
     print(f"# generated {a.lines} CSV lines in {time.time() - t0:.1f}s", file=sys.stderr, flush=True)
     bad = 0
     runs = []
@@ -134,7 +152,9 @@ def main() -> int:
             bad += not r["valid"]
             runs.append(r)
             print(json.dumps(r), flush=True)
-    out = {"job": "ScoreStats (CSV group-by: mean / max / count)", "lines": a.lines, "workers": a.workers,
+    what = {"scores": "ScoreStats (CSV group-by: mean / max / count)",
+            "latency": f"LatencyStats (p50 / p90 / p99 / max / count of {a.endpoints} endpoints, {a.splits} splits)"}
+    out = {"job": what[a.job], "lines": a.lines, "workers": a.workers,
            "storage": a.storage, "valid_runs": len(runs) - bad, "runs": len(runs)}
     for knob in (False, True):
         ok = [r for r in runs if r["valid"] and r["device_write"] == knob]

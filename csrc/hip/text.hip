@@ -308,8 +308,9 @@ __global__ void text_parse_i64_kernel(const u8* __restrict__ text, const long lo
       int nd = 0;
       for (; j < len && p[j] >= '0' && p[j] <= '9'; ++j, ++nd) a = a * 10 + (p[j] - '0');
       while (j < len && is_ws(p[j])) ++j;
-      bad = nd == 0 || j != len || nd > 19;
-      v = neg ? -(long long)a : (long long)a;
+      // at most 19 digit characters (a cannot wrap), and within int64: 2^63 only with a minus
+      bad = nd == 0 || j != len || nd > 19 || a > (1ull << 63) - (neg ? 0u : 1u);
+      v = (long long)(neg ? 0ull - a : a);  // negated as unsigned: no signed overflow at -2^63
     }
     out[i] = bad ? 0 : v;
     anybad |= bad;

@@ -167,7 +167,10 @@ def _parse_host(b: bytes, s: int, n: int, kind):
     if kind is int:
         if not (tok.lstrip("+-").isdigit()) or len(tok.lstrip("+-")) > 19:
             raise ValueError
-        return int(tok)
+        v = int(tok)
+        if not -2**63 <= v < 2**63:
+            raise ValueError
+        return v
     if any(c not in "0123456789+-.eE" for c in tok):
         raise ValueError
     return float(tok)
@@ -203,15 +206,24 @@ def _parse(text, starts, lens, kind, check: bool):
 
 def parse_f64(text: torch.Tensor, starts: torch.Tensor, lens: torch.Tensor, check: bool = False) -> torch.Tensor:
     """Decimal numbers of the spans as float64 (``[+-]digits[.digits][e[+-]digits]``
-    with surrounding whitespace): correctly rounded when the significant
-    digits fit 53 bits and the exponent is within +-22 (what Python's float()
-    gives), a few ulp off otherwise.  Malformed spans give NaN (``check``:
-    raise instead, one host synchronisation)."""
+    with surrounding Lua ``%s`` whitespace; at least one digit).  On the GPU:
+    exactly what Python's float() gives when the value is m * 10^k with
+    m < 2^53 (trailing zeros moved into k) and abs(k) <= 22, however it is
+    written; otherwise within 3 of float(), counted in steps of the double's
+    bit pattern (ulps, 2^-1074 among the subnormals), down to the smallest
+    subnormal; +-inf above the double range, +-0 below it (the sign of a zero
+    is kept).  Digits past the 19th significant one only move the exponent.
+    CPU tensors give float() itself.  Malformed spans, ``inf`` and ``nan``
+    among them, give NaN (``check``: raise instead, one host
+    synchronisation)."""
     return _parse(text, starts, lens, float, check)
 
 
 def parse_i64(text: torch.Tensor, starts: torch.Tensor, lens: torch.Tensor, check: bool = False) -> torch.Tensor:
-    """Decimal integers of the spans as int64 (malformed: 0, or raise with ``check``)."""
+    """Decimal integers of the spans as int64: ``[+-]digits`` with surrounding
+    whitespace, at most 19 digit characters, value in [-2^63, 2^63 - 1].
+    Anything else (a decimal point, an exponent, 20 digits, 2^63) is malformed:
+    0, or raise with ``check``."""
     return _parse(text, starts, lens, int, check)
 
 

@@ -889,6 +889,10 @@ static unsigned g_ins_cap = 65536u;
 static bool g_agg_batch = false;
 // agg_combine_kernel<false, PH> (Tunables.agg_phases, MR_AGG_PHASES)
 static int g_agg_phases = 1;
+// rows per block of agg_combine_kernel (0 = chosen from n; mr_agg_set_rows)
+static int g_agg_rows = 0;
+// rows per block of the last mr_agg_insert launch (0: agg_insert_kernel; mr_agg_last_rows)
+static int g_agg_last_rows = 0;
 
 extern "C" {
 
@@ -908,6 +912,19 @@ int mr_agg_set_phases(int ph) {
   g_agg_phases = ph;
   return 0;
 }
+
+// Launch knob of the LDS-combined fold: rows per block (0 = auto: 4096, or
+// fewer so the grid has >= 1024 blocks; otherwise 512, 1024, 2048 or 4096).
+int mr_agg_set_rows(int rows) {
+  if (rows != 0 && rows != 512 && rows != 1024 && rows != 2048 && rows != 4096) return -1;
+  g_agg_rows = rows;
+  return 0;
+}
+
+// What the last mr_agg_insert launched: the rows per block of
+// agg_combine_kernel, or 0 for the per-row agg_insert_kernel (tests observe
+// the path their rows took).
+int mr_agg_last_rows(void) { return g_agg_last_rows; }
 
 // Keys pre-encoded (hi, lo, rep + rep_add) — or, when `text` is given, byte
 // spans (starts int64, lens int32) of `text`, whose rep offsets are
@@ -942,6 +959,8 @@ int mr_agg_insert(void* tag, void* thi, void* tlo, void* tval, void* trep, void*
     // rows per block: 4096, or fewer (down to 512) so the grid has >= 1024 blocks
     u32 rows = (u32)CB_ROWS;
     while (rows > (u32)CB_T && (n + rows - 1) / rows < 1024) rows >>= 1;
+    if (g_agg_rows > 0) rows = (u32)g_agg_rows;
+    g_agg_last_rows = (int)rows;
     const u64 nb = (n + rows - 1) / rows;
     const GTab gt = ag_gtab(tag, thi, tlo, tval, trep, ctrl, cap, src);
     if (g_agg_batch)
@@ -958,6 +977,7 @@ int mr_agg_insert(void* tag, void* thi, void* tlo, void* tval, void* trep, void*
                          to_cols(a), rows);
     return (int)hipGetLastError();
   }
+  g_agg_last_rows = 0;
   hipLaunchKernelGGL(agg_insert_kernel, dim3(ag_grid(n, 256, g_ins_cap)), dim3(256), 0, stream,
                      ag_gtab(tag, thi, tlo, tval, trep, ctrl, cap, src), ks, n, to_cols(a));
   return (int)hipGetLastError();

@@ -22,7 +22,8 @@
 // first value is found by binary search in off[], narrowed to the segments of
 // the workgroup's tile (two searches per workgroup, in LDS broadcast).
 //
-// Empty segments keep the caller's fill (the fold's identity).
+// Empty segments keep the caller's fill (the fold's identity), and so does a
+// min / max list whose values are all NaN.
 #include <hip/hip_runtime.h>
 #include <climits>
 #include "mr_common.h"
@@ -40,6 +41,16 @@ __device__ __forceinline__ T fold(T a, T b, int op) {
   if (op == MIN) return b < a ? b : a;
   if (op == MAX) return b > a ? b : a;
   return a + b;
+}
+
+// min / max ignore a NaN value (IEEE minNum / maxNum): it becomes the fold's
+// identity as it is loaded, so a list's result depends neither on the order
+// of its values nor on where the thread boundaries fall (b < a alone keeps a
+// NaN that comes first and drops one that comes later).  Sums keep it.
+__device__ __forceinline__ long long live(long long v, int) { return v; }
+__device__ __forceinline__ double live(double v, int op) {
+  if (op == SUM || v == v) return v;
+  return op == MIN ? __builtin_inf() : -__builtin_inf();
 }
 
 template <typename T>
@@ -102,10 +113,10 @@ __global__ void __launch_bounds__(THREADS) seg_reduce_kernel(const long long* __
     T x[V];
     if (t0 + V <= n) {
 #pragma unroll
-      for (int k = 0; k < V; ++k) x[k] = val[t0 + k];
+      for (int k = 0; k < V; ++k) x[k] = live(val[t0 + k], op);
     } else {
 #pragma unroll
-      for (int k = 0; k < V; ++k) x[k] = t0 + k < n ? val[t0 + k] : T(0);
+      for (int k = 0; k < V; ++k) x[k] = t0 + k < n ? live(val[t0 + k], op) : T(0);
     }
     long long s = seg_of(off, sa, sb, t0);
     long long end = off[s + 1];

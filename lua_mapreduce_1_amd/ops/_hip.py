@@ -156,6 +156,8 @@ _SIGS = {
     "mr_wc3_set_dyn": [_i32],
     "mr_agg_set_batch": [_i32],
     "mr_agg_set_phases": [_i32],
+    "mr_agg_set_rows": [_i32],
+    "mr_agg_last_rows": [],
 }
 _RESTYPE_U64 = {"mr_compact_pack_ws_bytes", "mr_ii_unique_tiles", "mr_text_tiles", "mr_scan_partials_len", "mr_tail_pack_bytes", "mr_tail_ws_layout",
                 "mr_tail_bhist_bytes", "mr_onesweep_tiles", "mr_rec_tie_ws_words", "mr_sdma_d2h_begin",

@@ -15,6 +15,20 @@ verified byte for byte) and each slot holds either
   and divided when results are read), or
 * the list of every value emitted for it (``list`` mode): postings
   (slot, value) appended in emission order.
+
+The folds' contract, the same on the GPU (every kernel path) and on CPU
+tensors (docs/GUIDE.md section 4; tests/test_typed_folds.py):
+
+* ``sum``: i64 wraps modulo 2^64; a floating sum may be accumulated in any
+  order (within n*u*S / (1 - n*u) of the exact sum: n values of total
+  magnitude S, u = 2^-53 / 2^-24); any NaN, or both infinities, give NaN.
+* ``min`` / ``max``: exact; NaN values are ignored (IEEE minNum / maxNum),
+  a key whose values are all NaN holds the identity (+inf / -inf); -0.0 and
+  +0.0 compare equal, either may come back.
+* a source value is converted to its column's type before it is folded: an
+  integer into a floating column and f64 into f32 round to nearest, a
+  floating value into i64 truncates toward zero (finite, |v| < 2^63; NaN,
+  the infinities and values out of range into i64 are unspecified).
 """
 from __future__ import annotations
 
@@ -563,7 +577,9 @@ class AggTable:
             for (dt, op, _i), v in zip(self.cols_spec, cols):
                 npdt = v.dtype
                 agg = np.full(m, _identity(dt, op), npdt)
-                {"sum": np.add, "min": np.minimum, "max": np.maximum}[op].at(agg, inv, v)
+                # fmin / fmax: a NaN value is ignored (IEEE minNum / maxNum), as the device atomics do
+                with np.errstate(invalid="ignore", over="ignore"):
+                    {"sum": np.add, "min": np.fmin, "max": np.fmax}[op].at(agg, inv, v)
                 out.append(torch.from_numpy(agg))
         elif not self.list_mode:
             out = [torch.from_numpy(np.full(0, _identity(dt, op), {"i64": np.int64, "f64": np.float64,

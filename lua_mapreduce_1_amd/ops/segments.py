@@ -81,7 +81,15 @@ def _identity(dtype: torch.dtype, op: str):
 def reduce(off: torch.Tensor, val: torch.Tensor, op: str = "sum", empty=None) -> torch.Tensor:
     """Fold of every list (``op``: sum | min | max); an empty list gives
     ``empty`` (default: the fold's identity — 0, or the dtype's max / min).
-    int32 / float32 values fold as int64 / float64."""
+    int32 / float32 values fold as int64 / float64.
+
+    The typed folds' contract (docs/GUIDE.md section 4): an int64 sum wraps
+    modulo 2^64; a float64 sum may be accumulated in any order (within
+    n*u*S / (1 - n*u) of the exact sum, u = 2^-53), any NaN or both
+    infinities give NaN; min / max are exact and ignore NaN values wherever
+    they stand in the list (IEEE minNum / maxNum) — a list of NaNs only gives
+    the identity, +inf / -inf, like an empty one before ``empty`` is applied;
+    -0.0 and +0.0 compare equal, either may come back."""
     if op not in _OPS:
         raise ValueError(f"segment op {op!r}: one of {tuple(_OPS)}")
     _check(off, val)
@@ -106,8 +114,12 @@ def reduce(off: torch.Tensor, val: torch.Tensor, op: str = "sum", empty=None) ->
             ln = np.diff(o)
             nz = np.flatnonzero(ln > 0)
             if nz.size:
-                uf = {"sum": np.add, "min": np.minimum, "max": np.maximum}[op]
-                out.numpy()[nz] = uf.reduceat(v, o[:-1][nz])
+                uf = {"sum": np.add, "min": np.fmin, "max": np.fmax}[op]
+                if op != "sum" and v.dtype == np.float64:
+                    # a NaN is the identity of min / max (an all-NaN list keeps it)
+                    v = np.where(np.isnan(v), _identity(val.dtype, op), v)
+                with np.errstate(invalid="ignore", over="ignore"):
+                    out.numpy()[nz] = uf.reduceat(v, o[:-1][nz])
     if empty is not None and m:
         out = torch.where(lengths(off) > 0, out, torch.as_tensor(empty, dtype=out.dtype, device=out.device))
     return out

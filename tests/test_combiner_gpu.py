@@ -30,6 +30,12 @@ def test_seg_reduce_kernel_matches_numpy(gpu, seed, hot, dtype):
         got = S.reduce(o, v, op).cpu().numpy()
         exp = S.reduce(torch.from_numpy(off), torch.from_numpy(val), op).numpy()
         if dtype == "f64" and op == "sum":
+            # against the exact oracle (tests/test_typed_folds.py): within the derived bound of
+            # math.fsum for every list; the comparison with the CPU path stays alongside (for the
+            # long lists of these inputs the derived bound is the looser of the two)
+            from test_typed_folds import check
+            for s in np.flatnonzero(np.diff(off) > 0):
+                check("f64", "sum", got[s], val[off[s]:off[s + 1]].tolist(), (seed, s))
             assert np.allclose(got, exp, rtol=1e-9, atol=1e-6), op
         else:
             assert np.array_equal(got, exp), op

@@ -155,6 +155,20 @@ def test_agg_table_folds_gpu(gpu, dtype, skew):
         res[str(dev)] = {k: [x[i].item() for x in c] for i, k in enumerate(kb)}
     a, b = res["cpu"], res[str(gpu)]
     assert set(a) == set(b) == set(words[i] for i in np.unique(idx[lens.numpy() > 0]))
+    # both against the exact oracle of tests/test_typed_folds.py: sums within the derived bound of
+    # math.fsum (equal for i64), min / max equal
+    from test_typed_folds import check, to_column
+    rows: dict = {}
+    for i in np.flatnonzero(lens.numpy() > 0):
+        rows.setdefault(words[idx[i]], []).append(i)
+    vn = vals.numpy()
+    for k in a:
+        col = to_column(dtype, vn[rows[k]])
+        for j, op in enumerate(("sum", "min", "max")):
+            check(dtype, op, b[k][j], col, ("gpu", k))
+            check(dtype, op, a[k][j], col, ("cpu", k))
+        assert a[k][3] == b[k][3] == len(col)
+    # (kept alongside: for the hot keys of these inputs the derived bound is looser than this)
     for k in a:
         s0, s1 = a[k][0], b[k][0]
         if dtype == "i64":

@@ -40,8 +40,52 @@ def host_lib():
             L.mrh_load_wait.restype = ctypes.c_int
             L.mrh_drop_cache.argtypes = [ctypes.c_char_p]
             L.mrh_drop_cache.restype = ctypes.c_int
+            L.mrh_pack_plan.argtypes = [ctypes.c_int, P, P, ctypes.c_int, P, P, P, P]
+            L.mrh_pack_plan.restype = I64
+            L.mrh_pack_run.argtypes = [ctypes.c_int, P, P, P, P, P, P, ctypes.c_int]
+            L.mrh_pack_run.restype = ctypes.c_int
             _HOST = L
     return _HOST
+
+
+PACK_TABLE = 128  # bytes of one split's code table (code -> byte)
+
+
+class PackedSplits:
+    """Bit-packed copy of the splits of one host buffer (csrc/host/pack.cpp):
+    ``buffer`` holds split i as ``k[i]``-bit codes at ``offsets[i]`` (16-byte
+    aligned), ``nbytes[i]`` bytes long; ``tables[i]`` maps code -> byte.  A
+    split with more than 128 distinct byte values is raw: ``k[i] == 8``,
+    ``nbytes[i] == 0``, and it is read from the unpacked buffer."""
+
+    __slots__ = ("buffer", "offsets", "nbytes", "k", "tables")
+
+    def __init__(self, buffer, offsets, nbytes, k, tables):
+        self.buffer, self.offsets, self.nbytes, self.k, self.tables = buffer, offsets, nbytes, k, tables
+
+
+def pack_splits(buffer: torch.Tensor, offsets, threads: int = 8, pinned: bool = False) -> PackedSplits:
+    """Pack the splits ``buffer[offsets[i]:offsets[i+1]]`` of a host buffer
+    with the native packer.  ``pinned``: the packed buffer is allocated in
+    pinned memory of its exact size (:func:`pinned_empty`)."""
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = len(off) - 1
+    if n < 0 or (n and (off[0] < 0 or off[-1] > buffer.numel())):
+        raise ValueError("pack_splits: split offsets outside the buffer")
+    poff, pbytes = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64)
+    k = np.zeros(max(n, 1), dtype=np.int32)
+    tables = np.zeros((max(n, 1), PACK_TABLE), dtype=np.uint8)
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    L = host_lib()
+    src = ctypes.c_void_p(buffer.data_ptr())
+    total = int(L.mrh_pack_plan(n, src, ptr(off), int(threads), ptr(poff), ptr(pbytes), ptr(k), ptr(tables)))
+    if total < 0:
+        raise RuntimeError("mrh_pack_plan failed")
+    out = pinned_empty(total) if pinned else torch.empty(total, dtype=torch.uint8)
+    if L.mrh_pack_run(n, src, ptr(off), ptr(poff), ptr(k), ptr(tables), ctypes.c_void_p(out.data_ptr()),
+                      int(threads)) != 0:
+        raise RuntimeError("mrh_pack_run failed")
+    return PackedSplits(out, poff[:n], pbytes[:n], k[:n], tables[:n])
 
 
 class AsyncLoad:

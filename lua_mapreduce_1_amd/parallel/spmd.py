@@ -285,6 +285,9 @@ class SPMDEngine(StagingMixin, CheckpointMixin):
         self._rec_tmpl = None
         self.copy_stream, self.streams = _engine_streams(self.device)
         self._plans: dict = {}
+        # warm iterations ship the store's packed copy when it has one
+        self.pack_input = bool(self.params.get("pack_input", TUNABLES.pack_input))
+        self._pack_staging: list = [None] * N_ARENAS  # device staging buffers of packed bytes, one per arena
         # per slot (pipelined iterations alternate): device event timers, the
         # job ranges of the map chunks and their device error words
         self._timers: list = [None, None]

@@ -11,6 +11,8 @@ stay resident in HBM across iterations.
 """
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 import torch
 
@@ -32,10 +34,13 @@ class StagingMixin:
         at split boundaries, sizes ramping up (the first copy is exposed), big
         in the middle, ramping down at the end (the last kernel is exposed) —
         also for small per-rank inputs.  Returns (split bounds, arena views,
-        pinned host views, reusable events)."""
+        pinned host views, reusable events, first split, the packed half of
+        the plan or None: _plan_unpack)."""
         a, b = self.splits.region(ids[0], ids[-1] + 1)
         nbytes = b - a
         if self.arenas[slot] is None or self.arenas[slot].numel() < nbytes:
+            if self._pack_staging[slot] is not None:  # (as in _plan_unpack: unpacks of dropped plans finish first)
+                self.copy_stream.synchronize()
             self.arenas[slot] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             self._arena_holds.pop(slot, None)
             self._plans = {k: v for k, v in self._plans.items() if k[2] != slot}
@@ -74,10 +79,77 @@ class StagingMixin:
             views.append(arena[ca - a:cb - a])
             host_views.append(host[ca:cb])
             events.append(torch.cuda.Event() if self.copy_stream is not None else None)
-        return bounds, views, host_views, events, ids[0]
+        pk = self._plan_unpack(ids, slot, bounds) if self._ships_packed() else None
+        return bounds, views, host_views, events, ids[0], pk
+
+    def _ships_packed(self) -> bool:
+        """Warm iterations ship the store's packed copy (``MR_PACK_INPUT`` /
+        ``params["pack_input"]`` / ``engine.pack_input``) when it has one."""
+        return (self.copy_stream is not None and bool(getattr(self, "pack_input", TUNABLES.pack_input))
+                and getattr(self.splits, "packed", None) is not None)
+
+    def _plan_unpack(self, ids: list[int], slot: int, bounds):
+        """The packed half of a copy plan: the slot's device staging buffer for
+        the packed bytes of the range, the unpack descriptors and code tables
+        (uploaded here, once per cached plan), and per chunk the packed host ->
+        staging copy, the raw host -> arena copies of its raw splits (more than
+        128 distinct byte values: never packed) and its descriptor range."""
+        st = self.splits
+        pk = st.packed
+        l0 = ids[0] - st.own[0]
+        n = len(ids)
+        poff, pby, kk = pk.offsets[l0:l0 + n], pk.nbytes[l0:l0 + n], pk.k[l0:l0 + n]
+        a = st.region(ids[0], ids[0] + 1)[0]
+        dst = st.offsets[ids[0]:ids[0] + n] - st.base - a
+        size = st.offsets[ids[0] + 1:ids[0] + n + 1] - st.offsets[ids[0]:ids[0] + n]
+        p_a = int(poff[0])
+        p_b = max(int((poff + pby).max()), p_a)
+        need = max(p_b - p_a, 16)
+        stg = self._pack_staging[slot]
+        if stg is None or stg.numel() < need:
+            if stg is not None:
+                # the slot's earlier plans (dropped below) may still have copies
+                # and unpacks in flight that use the old buffer, their
+                # descriptors and tables: let them finish before the allocator
+                # gets that memory back (it knows nothing of the copy stream)
+                self.copy_stream.synchronize()
+            stg = self._pack_staging[slot] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._plans = {k: v for k, v in self._plans.items() if k[2] != slot}
+        packed = np.flatnonzero(kk < 8)
+        if (pby[packed] != (size[packed] + 15) // 16 * 2 * kk[packed]).any() or (poff % 16).any() or \
+                (poff[packed] + pby[packed] > pk.buffer.numel()).any():
+            raise ValueError("packed split store: sizes or offsets do not match the split layout")
+        desc = np.zeros((len(packed), 4), dtype=np.int64)
+        desc[:, 0] = poff[packed] - p_a
+        desc[:, 1] = dst[packed]
+        desc[:, 2] = size[packed]
+        desc[:, 3] = kk[packed].astype(np.int64) | ((np.arange(len(packed), dtype=np.int64) * 128) << 32)
+        tables = np.ascontiguousarray(pk.tables[l0:l0 + n][packed]).reshape(-1)
+        first = np.searchsorted(packed, np.asarray(bounds))  # descriptor range of every chunk
+        chunks = []
+        for i in range(len(bounds) - 1):
+            b0, b1 = bounds[i], bounds[i + 1]
+            ca = int(poff[b0]) - p_a
+            cb = max(int((poff[b0:b1] + pby[b0:b1]).max()), int(poff[b0])) - p_a
+            raw = []
+            for j in np.flatnonzero(kk[b0:b1] >= 8):  # (runs of raw splits are rare: one copy each)
+                ra, rb = st.region(ids[0] + b0 + int(j), ids[0] + b0 + int(j) + 1)
+                raw.append((self.arenas[slot][ra - a:rb - a], st.buffer[ra:rb]))
+            d0, d1 = int(first[i]), int(first[i + 1])
+            chunks.append({"dev": stg[ca:cb], "host": pk.buffer[p_a + ca:p_a + cb], "raw": raw, "d0": d0,
+                           "nd": d1 - d0, "max_n": int(desc[d0:d1, 2].max()) if d1 > d0 else 0})
+        dev = self.device
+        return {"staging": stg, "chunks": chunks, "slot": slot,
+                "desc": torch.from_numpy(desc).to(dev) if len(packed) else torch.zeros((1, 4), dtype=torch.int64,
+                                                                                        device=dev),
+                "tables": torch.from_numpy(tables).to(dev) if len(packed) else torch.zeros(128, dtype=torch.uint8,
+                                                                                            device=dev)}
+
+    def _plan_key(self, ids: list[int], slot: int, single: bool):
+        return (ids[0], len(ids), slot, single, self._ships_packed())
 
     def _get_plan(self, ids: list[int], slot: int, single: bool = False):
-        key = (ids[0], len(ids), slot, single)
+        key = self._plan_key(ids, slot, single)
         plan = self._plans.get(key)
         if plan is None and self.copy_stream is not None and self._can_pipeline() and self.prime_plans and not getattr(
                 self, "_priming", False):
@@ -106,7 +178,7 @@ class StagingMixin:
         return plan
 
     def _issue_copies(self, plan, wait_for=None) -> None:
-        bounds, views, host_views, events, id0 = plan
+        bounds, views, host_views, events, id0, pk = plan
         streaming = not self.splits.all_ready()
         cs = self.copy_stream
         if wait_for is not None:
@@ -117,12 +189,46 @@ class StagingMixin:
             cs.wait_event(ev0)
         from ..ops import _hip
         sp = _hip.stream_ptr(cs)
+        if pk is not None and not streaming:
+            self._issue_packed(pk, events, sp)
+            return
         for i, (dst, src, ev) in enumerate(zip(views, host_views, events)):
             if streaming:  # the native loader is still reading: copy each chunk once it has landed
                 self.splits.wait_ready(id0 + bounds[i], id0 + bounds[i + 1])
             # direct hipMemcpyAsync (pinned -> HBM) instead of copy_: no
             # host-allocator event bookkeeping per chunk (it stalled the host)
             _hip.call("mr_memcpy_async", _hip.ptr(dst), _hip.ptr(src), dst.numel(), 1, sp)
+            ev.record(cs)
+
+    def _issue_packed(self, pk, events, sp) -> None:
+        """A plan's copies from the packed store: per chunk one copy of its
+        packed bytes into the slot's staging buffer (and its raw splits
+        straight into the arena), then the chunk's unpack, all on the copy
+        stream; the chunk's event — what the map waits on — is recorded behind
+        the unpack.
+
+        The unpack runs on the copy stream itself, not on a stream of its own:
+        the link then idles for the unpack (0.11 ms of a 3.9 ms copy for the
+        whole benchmark corpus), but a fifth stream has to share one of the
+        process's four hardware queues, and there the unpack's wait for its
+        copy held back the other iteration's map and tail — 0.45 ms of link
+        gaps per step and an inverted-index step 19 % slower than with raw
+        bytes (profiles/input_pack/README.md).  Stream order also settles the
+        reuse of the staging buffer, which is one per arena slot and shared by
+        the slot's plans: a later copy into it is queued behind every unpack
+        that reads it."""
+        from ..ops import _hip
+        cs = self.copy_stream
+        stg, arena, desc, tables = pk["staging"], self.arenas[pk["slot"]], pk["desc"], pk["tables"]
+        for c, ev in zip(pk["chunks"], events):
+            if c["dev"].numel():
+                _hip.call("mr_memcpy_async", _hip.ptr(c["dev"]), _hip.ptr(c["host"]), c["dev"].numel(), 1, sp)
+            for dst, src in c["raw"]:
+                _hip.call("mr_memcpy_async", _hip.ptr(dst), _hip.ptr(src), dst.numel(), 1, sp)
+            if c["nd"]:
+                _hip.call("mr_unpack_splits", _hip.ptr(stg), stg.numel(), _hip.ptr(arena), arena.numel(),
+                          ctypes.c_void_p(desc.data_ptr() + 32 * c["d0"]), c["nd"], c["max_n"], _hip.ptr(tables),
+                          tables.numel(), sp)
             ev.record(cs)
 
     def _copy_gate_event(self):
@@ -308,7 +414,7 @@ class StagingMixin:
                 yield (j0, j0 + len(ids)), self.arena[:b - a]
                 return
             plan = self._get_plan(ids, self.slot, single=prefetched and _PREFETCH_SINGLE)
-            bounds, views, host_views, events, _ = plan
+            bounds, views, host_views, events, _, _ = plan
             if cs is not None and not prefetched and not self.splits.all_ready():
                 # input still being read from files (cold start): each chunk is
                 # copied as soon as its splits have landed and mapped right

@@ -99,6 +99,11 @@ class Tunables:
                               "exchange, result download) instead of four times")
     pipeline: bool = _knob("MR_PIPELINE", True, "bench/proxies: map of iteration i+1 overlaps the tail of i")
     prefetch_single: bool = _knob("MR_PREFETCH_SINGLE", True, "prefetched inputs: one DMA per iteration")
+    pack_input: bool = _knob("MR_PACK_INPUT", True,
+                             "pinned split stores keep a second, bit-packed copy of every split (fixed-width codes "
+                             "of its alphabet, csrc/host/pack.cpp) made once when loading finishes; iterations "
+                             "ship that copy over PCIe and a kernel restores the bytes in the arena (csrc/hip/"
+                             "unpack.hip).  Off: raw bytes are shipped, no packed buffer, no extra launches")
     sdma_min_mb: float = _knob("MR_SDMA_MIN_MB", 8.0,
                                "result downloads of at least this many MiB go over the SDMA copy engines (ROCr copy "
                                "API, csrc/hip/sdma.hip) after the tail's kernels, not as a runtime blit kernel on "

@@ -8,8 +8,8 @@ sorted values, as numpy's default).  The reference runs such a reducer per
 key in Lua over the grouped values (/root/reference/mapreduce/job.lua:264-284);
 here ``reducefn`` is that per-key form (server/worker host plane, the oracle)
 and ``device_reducefn`` the same reducer over every key's list at once: one
-segmented sort of all lists (ops/segments.py) and gathers at the percentile
-positions.  There is no combiner (a percentile does not combine), so every
+segmented sort of all lists and one pick of the three percentiles
+(ops/segments.py ``sort`` / ``quantiles``).  There is no combiner (a percentile does not combine), so every
 value is shipped to its reducer, as the reference does without one.
 
 * ``device_mapfn``: ``emit.csv`` — key field 0, value field 1 (float64
@@ -103,22 +103,14 @@ def reducefn(key, values, emit):
 
 def device_reducefn(keys, off, val):
     """Every key's [p50, p90, p99, max, count] at once: one segmented sort of
-    all value lists, then gathers at the interpolation positions."""
+    all value lists, then the three percentiles of every list in one pick."""
     import torch
     from lua_mapreduce_1_amd.ops import segments as S
     ln = S.lengths(off)
-    sv = S.sort(off, val).to(torch.float64)
+    sv = S.sort(off, val)
     last = (off[1:] - 1).clamp(min=0)
-    cols = []
-    for q in QS:
-        pos = (ln - 1).clamp(min=0).to(torch.float64) * q
-        lo = pos.floor().to(torch.int64)
-        hi = pos.ceil().to(torch.int64)
-        a, b = sv[off[:-1] + lo], sv[off[:-1] + hi]
-        cols.append(a + (b - a) * (pos - lo.to(torch.float64)))
-    cols.append(sv[last])
-    cols.append(ln.to(torch.float64))
-    return torch.stack(cols, dim=1)
+    pct = S.quantiles(off, sv, QS, sorted=True)
+    return torch.cat([pct, sv[last].to(torch.float64)[:, None], ln.to(torch.float64)[:, None]], dim=1)
 
 
 def finalfn(pairs_iterator):

@@ -122,6 +122,9 @@ _SIGS = {
     "mr_exact_hash": [_p, _p, _p, _p, _u64, _p, _p],
     "mr_exact_fix": [_p, _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p],
     "mr_seg_reduce": [_p, _u64, _p, _u64, _i32, _i32, _p, _p],
+    "mr_seg_sort": [_p, _u64, _p, _u64, _i32, _i32, _p, _p, _p],
+    "mr_seg_sort_tile": [],
+    "mr_seg_pick": [_p, _u64, _p, _u64, _i32, ctypes.POINTER(ctypes.c_double), _i32, _p, _p],
     "mr_posting_keys": [_p, ctypes.c_longlong, _p, ctypes.c_longlong, ctypes.c_longlong, _p, _p, _p],
     "mr_csv_set_config": [_i32, _i32],
     "mr_agg_set_insert_grid": [_i32],

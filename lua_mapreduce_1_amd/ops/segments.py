@@ -13,9 +13,13 @@ job.lua:264-284); these helpers fold ALL of a rank's lists at once:
   segmented scan of the partial folds, one atomic per crossing segment and
   wavefront — skew-proof for hot keys), NumPy ``reduceat`` on CPU tensors;
 * :func:`count`, :func:`mean`, :func:`first`, :func:`last`;
-* :func:`sort` (values ordered inside each list: one stable radix sort by
-  (segment, value)), :func:`unique`, :func:`nunique`, :func:`topk`,
-  :func:`median`, :func:`quantile`;
+* :func:`sort` (values ordered inside each list: ``mr_seg_sort``,
+  csrc/hip/segsort.hip — tiles of ``SORT_TILE`` values sorted in LDS, then
+  merge passes over the lists that cross tiles, work split by values; with
+  ``MR_SEG_SORT=0``, other dtypes and :func:`sort_perm`, one stable radix
+  sort by (segment, value)), :func:`unique`, :func:`nunique`, :func:`topk`;
+* :func:`quantiles` (several quantiles of every list from one sort and one
+  ``mr_seg_pick`` launch), :func:`quantile`, :func:`median`;
 * :func:`ids` (segment of every value), :func:`from_lengths`, :func:`take`
   (per-list slices).
 
@@ -25,11 +29,13 @@ sync unless noted) and on CPU tensors (the executable specification).
 from __future__ import annotations
 
 import builtins as _builtins
+import ctypes
 
 import numpy as np
 import torch
 
 from . import _hip
+from ..utils.config import TUNABLES
 
 _I64_MAX, _I64_MIN = (1 << 63) - 1, -(1 << 63)
 _OPS = {"sum": 0, "min": 1, "max": 2}
@@ -189,9 +195,34 @@ def sort_perm(off: torch.Tensor, val: torch.Tensor, descending: bool = False) ->
     return sort_keys_checked([ids(off, n), k], bits=[_bits(m), 64]).long()
 
 
+def _native(val: torch.Tensor) -> bool:
+    """The values go through csrc/hip/segsort.hip (MR_SEG_SORT, on by default)."""
+    return val.is_cuda and val.dtype in (torch.int64, torch.float64) and TUNABLES.seg_sort
+
+
+def __getattr__(name: str):
+    if name == "SORT_TILE":  # values per workgroup tile of mr_seg_sort; None without the library
+        try:
+            return int(_hip.lib().mr_seg_sort_tile())
+        except (OSError, RuntimeError, AttributeError):
+            return None
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def sort(off: torch.Tensor, val: torch.Tensor, descending: bool = False) -> torch.Tensor:
-    """Every list's values in ascending (or descending) order (same ``off``)."""
-    return val[sort_perm(off, val, descending)] if val.numel() else val.clone()
+    """Every list's values in ascending (or descending) order (same ``off``).
+    int64 / float64 lists on the GPU: ``mr_seg_sort`` (tiles sorted in LDS,
+    then merge passes over the lists that cross tiles; no host sync)."""
+    n, m = val.numel(), off.numel() - 1
+    if n and m > 0 and _native(val):
+        _check(off, val)
+        off = off.to(torch.int64).contiguous()
+        val = val.contiguous()
+        out, tmp = torch.empty_like(val), torch.empty_like(val)
+        _hip.call("mr_seg_sort", _hip.ptr(off), m, _hip.ptr(val), n, 0 if val.dtype == torch.int64 else 1,
+                  1 if descending else 0, _hip.ptr(out), _hip.ptr(tmp), _hip.stream(val.device))
+        return out
+    return val[sort_perm(off, val, descending)] if n else val.clone()
 
 
 def take(off: torch.Tensor, val: torch.Tensor, start, stop) -> tuple[torch.Tensor, torch.Tensor]:
@@ -220,8 +251,7 @@ def unique(off: torch.Tensor, val: torch.Tensor) -> tuple[torch.Tensor, torch.Te
     m = off.numel() - 1
     if n == 0:
         return off.clone(), val.clone()
-    p = sort_perm(off, val)
-    sv = val[p]
+    sv = sort(off, val)
     seg = ids(off, n)  # segments do not move: the sort keeps lists in place
     keep = torch.ones(n, dtype=torch.bool, device=val.device)
     keep[1:] = (seg[1:] != seg[:-1]) | (order_key(sv[1:]) != order_key(sv[:-1]))
@@ -241,19 +271,44 @@ def topk(off: torch.Tensor, val: torch.Tensor, k: int, largest: bool = True) -> 
     return take(off, sort(off, val, descending=largest), 0, int(k))
 
 
+def quantiles(off: torch.Tensor, val: torch.Tensor, qs, sorted: bool = False) -> torch.Tensor:  # noqa: A002
+    """Linear-interpolated quantiles of every list -> float64 [m, len(qs)]
+    (NaN for an empty list): with ``pos = (len - 1) * q``, the value
+    ``a + (b - a) * (pos - floor(pos))`` between the sorted values a, b at
+    floor(pos) and ceil(pos), every operation rounded on its own.  One sort
+    for all of ``qs`` (none with ``sorted=True``: ``val`` is already sorted
+    inside each list) and, on the GPU, one ``mr_seg_pick`` launch."""
+    _check(off, val)
+    qs = [float(q) for q in qs]
+    m = off.numel() - 1
+    sv = val if sorted else sort(off, val)
+    if sv.dtype != torch.int64:
+        sv = sv.to(torch.float64)
+    out = torch.full((m, len(qs)), float("nan"), dtype=torch.float64, device=val.device)
+    if m == 0 or not qs or sv.numel() == 0:
+        return out
+    if _native(sv):
+        off = off.to(torch.int64).contiguous()
+        sv = sv.contiguous()
+        _hip.call("mr_seg_pick", _hip.ptr(off), m, _hip.ptr(sv), sv.numel(), 0 if sv.dtype == torch.int64 else 1,
+                  (ctypes.c_double * len(qs))(*qs), len(qs), _hip.ptr(out), _hip.stream(sv.device))
+        return out
+    sv = sv.to(torch.float64)
+    ln = lengths(off)
+    for j, q in enumerate(qs):
+        pos = (ln - 1).clamp(min=0).to(torch.float64) * q
+        lo = pos.floor().to(torch.int64)
+        hi = pos.ceil().to(torch.int64)
+        a = sv[(off[:-1] + lo).clamp(max=sv.numel() - 1)]
+        b = sv[(off[:-1] + hi).clamp(max=sv.numel() - 1)]
+        r = a + (b - a) * (pos - lo.to(torch.float64))
+        out[:, j] = torch.where(ln > 0, r, torch.full_like(r, float("nan")))
+    return out
+
+
 def quantile(off: torch.Tensor, val: torch.Tensor, q: float) -> torch.Tensor:
     """Linear-interpolated q-quantile of every list (float64; NaN if empty)."""
-    ln = lengths(off)
-    sv = sort(off, val).to(torch.float64)
-    if sv.numel() == 0:
-        return torch.full((ln.numel(),), float("nan"), dtype=torch.float64, device=val.device)
-    pos = (ln - 1).clamp(min=0).to(torch.float64) * float(q)
-    lo = pos.floor().to(torch.int64)
-    hi = pos.ceil().to(torch.int64)
-    a = sv[(off[:-1] + lo).clamp(max=sv.numel() - 1)]
-    b = sv[(off[:-1] + hi).clamp(max=sv.numel() - 1)]
-    r = a + (b - a) * (pos - lo.to(torch.float64))
-    return torch.where(ln > 0, r, torch.full_like(r, float("nan")))
+    return quantiles(off, val, (q,))[:, 0]
 
 
 def median(off: torch.Tensor, val: torch.Tensor) -> torch.Tensor:

@@ -113,6 +113,11 @@ class Tunables:
                                    "are encoded by one kernel straight into the worker's device arena (csrc/hip/"
                                    "ipc.hip mr_mrc1_encode, mr_mrc2_encode for a column spec) instead of downloaded, "
                                    "encoded on the host and uploaded")
+    seg_sort: bool = _knob("MR_SEG_SORT", True,
+                           "batched reducers: ops/segments.sort (and unique, topk, quantiles, median on it) of int64 / "
+                           "float64 lists on the GPU runs the segmented merge sort of csrc/hip/segsort.hip and "
+                           "quantiles its pick kernel.  Off: one global radix sort by (list, value) and torch "
+                           "gathers (tools/bench_segsort.py times one against the other)")
     spin_us: float = _knob("MR_SPIN_US", 2000.0, "host spin on completion words before hipStreamSynchronize, us")
     rec_chunks: int = _knob("MR_REC_CHUNKS", 3,
                             "record plane at W > 1 (R <= W partitions, sampled splitters): rounds of the exchange "

@@ -162,6 +162,7 @@ _SIGS = {
     "mr_agg_set_rows": [_i32],
     "mr_agg_last_rows": [],
     "mr_unpack_splits": [_p, _u64, _p, _u64, _p, _u64, _u64, _p, _u64, _p],
+    "mr_undict_splits": [_p, _u64, _p, _u64, _p, _u64, _u64, _p, _u64, _p, _u64, _p],
 }
 _RESTYPE_U64 = {"mr_compact_pack_ws_bytes", "mr_ii_unique_tiles", "mr_text_tiles", "mr_scan_partials_len", "mr_tail_pack_bytes", "mr_tail_ws_layout",
                 "mr_tail_bhist_bytes", "mr_onesweep_tiles", "mr_rec_tie_ws_words", "mr_sdma_d2h_begin",

@@ -44,6 +44,18 @@ def host_lib():
             L.mrh_pack_plan.restype = I64
             L.mrh_pack_run.argtypes = [ctypes.c_int, P, P, P, P, P, P, ctypes.c_int]
             L.mrh_pack_run.restype = ctypes.c_int
+            L.mrh_dict_build.argtypes = [ctypes.c_int, P, P, ctypes.c_int, I64]
+            L.mrh_dict_build.restype = P
+            L.mrh_dict_entries.argtypes = [P]
+            L.mrh_dict_entries.restype = I64
+            L.mrh_dict_slots.argtypes = [P, P]
+            L.mrh_dict_slots.restype = ctypes.c_int
+            L.mrh_dict_plan.argtypes = [P, ctypes.c_int, P, P, ctypes.c_int, P, P]
+            L.mrh_dict_plan.restype = ctypes.c_int
+            L.mrh_dict_run.argtypes = [P, ctypes.c_int, P, P, P, P, ctypes.c_int]
+            L.mrh_dict_run.restype = ctypes.c_int
+            L.mrh_dict_free.argtypes = [P]
+            L.mrh_dict_free.restype = None
             _HOST = L
     return _HOST
 
@@ -86,6 +98,77 @@ def pack_splits(buffer: torch.Tensor, offsets, threads: int = 8, pinned: bool = 
                       int(threads)) != 0:
         raise RuntimeError("mrh_pack_run failed")
     return PackedSplits(out, poff[:n], pbytes[:n], k[:n], tables[:n])
+
+
+DICT_SLOT = 32  # bytes of one dictionary entry on the device (bytes 0..30 the entry, byte 31 its length)
+DICT_MAX_ENTRIES = 1 << 20
+DICT_TILE_UNITS, DICT_TILE_BYTES = 4096, 8192
+
+
+class DictSplits:
+    """Dictionary-coded copy of the splits of one host buffer (csrc/host/
+    dictpack.cpp).  ``slots`` is the dictionary (``[entries, 32]`` uint8).
+    Split i is in this form when ``nbytes[i] > 0``: ``buffer`` holds its
+    ``units[i]`` 16-bit code units at ``offsets[i]`` (16-byte aligned), and rows
+    ``trow[i] .. trow[i] + tiles[i]`` (inclusive: one closing row) of ``tix``
+    (``[rows, 2]`` uint32: first unit, first output byte) are its tile index.
+    Every other split has ``nbytes[i] == 0`` and is shipped k-bit or raw."""
+
+    __slots__ = ("buffer", "offsets", "nbytes", "units", "tiles", "trow", "tix", "slots", "seconds")
+
+    def __init__(self, buffer, offsets, nbytes, units, tiles, trow, tix, slots, seconds=0.0):
+        self.buffer, self.offsets, self.nbytes, self.units = buffer, offsets, nbytes, units
+        self.tiles, self.trow, self.tix, self.slots, self.seconds = tiles, trow, tix, slots, seconds
+
+
+def dict_pack_splits(buffer: torch.Tensor, offsets, other_bytes=None, threads: int = 16, pinned: bool = False,
+                     max_entries: int = DICT_MAX_ENTRIES, force: bool = False) -> DictSplits:
+    """Code the splits ``buffer[offsets[i]:offsets[i+1]]`` against one
+    dictionary of their own tokens.  ``other_bytes[i]`` is what split i costs
+    in its smallest other form (default: its raw size); a split is kept in the
+    dictionary form only where that is strictly smaller (``force``: every
+    non-empty split is kept, whatever it costs: the decoder's tests).
+    ``pinned``: the code buffer is allocated in pinned memory of its exact
+    size."""
+    t0 = time.perf_counter()
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = len(off) - 1
+    if n < 0 or (n and (off[0] < 0 or off[-1] > buffer.numel())):
+        raise ValueError("dict_pack_splits: split offsets outside the buffer")
+    size = off[1:] - off[:-1]
+    other = size if other_bytes is None else np.minimum(np.asarray(other_bytes, dtype=np.int64), size)
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    L = host_lib()
+    src = ctypes.c_void_p(buffer.data_ptr())
+    h = L.mrh_dict_build(n, src, ptr(off), int(threads), int(max_entries))
+    if not h:
+        raise RuntimeError("mrh_dict_build failed")
+    try:
+        slots = np.zeros((int(L.mrh_dict_entries(h)), DICT_SLOT), dtype=np.uint8)
+        units, tiles = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64)
+        if L.mrh_dict_slots(h, ptr(slots)) != 0 or L.mrh_dict_plan(h, n, src, ptr(off), int(threads), ptr(units),
+                                                                    ptr(tiles)) != 0:
+            raise RuntimeError("mrh_dict_plan failed")
+        units, tiles = units[:n], tiles[:n]
+        take = (units > 0) if force else (units >= 0) & (2 * units < other)
+        nbytes = np.where(take, 2 * units, 0)
+        uoff = np.zeros(n, dtype=np.int64)
+        np.cumsum(((nbytes + 15) & ~15)[:-1], out=uoff[1:])
+        total = int(uoff[-1] + ((nbytes[-1] + 15) & ~15)) if n else 0
+        rows = np.where(take, tiles + 1, 0)
+        trow = np.zeros(n, dtype=np.int64)
+        np.cumsum(rows[:-1], out=trow[1:])
+        tix = np.zeros((max(int(rows.sum()), 1), 2), dtype=np.uint32)
+        out = pinned_empty(total) if pinned else torch.empty(total, dtype=torch.uint8)
+        u_arg = np.ascontiguousarray(np.where(take, uoff, -1), dtype=np.int64)
+        t_arg = np.ascontiguousarray(trow, dtype=np.int64)
+        if L.mrh_dict_run(h, n, ptr(u_arg), ptr(t_arg), ctypes.c_void_p(out.data_ptr()), ptr(tix),
+                          int(threads)) != 0:
+            raise RuntimeError("mrh_dict_run failed")
+    finally:
+        L.mrh_dict_free(h)
+    return DictSplits(out, uoff, nbytes, np.where(take, units, 0), np.where(take, tiles, 0), trow, tix, slots,
+                      time.perf_counter() - t0)
 
 
 class AsyncLoad:

@@ -45,9 +45,16 @@ class SplitStore:
     iterations (bench.py, tools/bench_*.py) does, and other drivers ship raw
     bytes until they do too.  The packer makes two passes over the buffer,
     about 1.1 s for 291 MB with 8 threads, so it pays only when the store is
-    staged many times (each re-staging of that corpus saves about 0.7 ms)."""
+    staged many times (each re-staging of that corpus saves about 0.7 ms).
+
+    With ``MR_PACK_DICT`` the store also keeps a dictionary-coded copy
+    (:attr:`dict_packed`, ops/io.py ``DictSplits``, csrc/host/dictpack.cpp):
+    whole tokens coded as 16-bit units against one dictionary of the store's
+    own tokens.  A split is held there only where that form is smaller than
+    its k-bit and raw forms; the k-bit copy stays complete."""
 
     packed = None  # PackedSplits of the owned splits, once finish_loading() has packed them
+    dict_packed = None  # DictSplits of the owned splits (MR_PACK_DICT), made beside the packed copy
     _pinned = False
     _threads = 8
 
@@ -145,19 +152,29 @@ class SplitStore:
             self._load.wait()
             self._load = None
 
-    def finish_loading(self, pack: bool | None = None) -> None:
+    def finish_loading(self, pack: bool | None = None, pack_dict: bool | None = None) -> None:
         """Wait for the loader; then, once, make the packed copy of the owned
-        splits (``pack``: default ``MR_PACK_INPUT`` for a pinned store).
-        Nothing is packed before the last split has landed, so an iteration
-        that runs while the store loads ships raw bytes."""
+        splits (``pack``: default ``MR_PACK_INPUT`` for a pinned store) and,
+        beside it, the dictionary-coded copy (``pack_dict``: default
+        ``MR_PACK_DICT``; only where the packed copy is made).  Nothing is
+        packed before the last split has landed, so an iteration that runs
+        while the store loads ships raw bytes."""
         self._finish_reads()
         if pack is None:
             pack = TUNABLES.pack_input and self._pinned
-        if pack and self.packed is None and self.buffer is not None and self.buffer.numel():
+        if pack_dict is None:
+            pack_dict = TUNABLES.pack_dict
+        if pack and self.buffer is not None and self.buffer.numel():
             from ..ops import io as mio
             i0, i1 = self.own
-            self.packed = mio.pack_splits(self.buffer, self.offsets[i0:i1 + 1] - self.base, threads=self._threads,
-                                          pinned=self._pinned)
+            off = self.offsets[i0:i1 + 1] - self.base
+            if self.packed is None:
+                self.packed = mio.pack_splits(self.buffer, off, threads=self._threads, pinned=self._pinned)
+            if pack_dict and self.dict_packed is None:
+                pk = self.packed
+                other = np.where(pk.k < 8, pk.nbytes, off[1:] - off[:-1])
+                self.dict_packed = mio.dict_pack_splits(self.buffer, off, other, threads=max(self._threads, 16),
+                                                        pinned=self._pinned)
 
     def newline_counts(self, i0: int, i1: int) -> list[int]:
         """Newlines of each owned split [i0, i1) (its padding newline included)."""

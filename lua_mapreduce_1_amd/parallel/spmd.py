@@ -287,7 +287,9 @@ class SPMDEngine(StagingMixin, CheckpointMixin):
         self._plans: dict = {}
         # warm iterations ship the store's packed copy when it has one
         self.pack_input = bool(self.params.get("pack_input", TUNABLES.pack_input))
+        self.pack_dict = bool(self.params.get("pack_dict", TUNABLES.pack_dict))  # (only where pack_input is on)
         self._pack_staging: list = [None] * N_ARENAS  # device staging buffers of packed bytes, one per arena
+        self._dict_dev = None  # (DictSplits, its dictionary and tile index on the device)
         # per slot (pipelined iterations alternate): device event timers, the
         # job ranges of the map chunks and their device error words
         self._timers: list = [None, None]

@@ -88,23 +88,88 @@ class StagingMixin:
         return (self.copy_stream is not None and bool(getattr(self, "pack_input", TUNABLES.pack_input))
                 and getattr(self.splits, "packed", None) is not None)
 
+    def _ships_dict(self) -> bool:
+        """Beside the packed copy, warm iterations ship the store's
+        dictionary-coded copy (``MR_PACK_DICT`` / ``params["pack_dict"]`` /
+        ``engine.pack_dict``) when it has one."""
+        return (self._ships_packed() and bool(getattr(self, "pack_dict", TUNABLES.pack_dict))
+                and getattr(self.splits, "dict_packed", None) is not None)
+
+    def _dict_on_device(self, dk):
+        """The store's dictionary and tile index in HBM, uploaded once per
+        engine, after the tile index has been checked against the limits the
+        decoder relies on (csrc/hip/undict.hip)."""
+        held = self._dict_dev
+        if held is not None and held[0] is dk:
+            return held[1], held[2]
+        from ..ops import io as mio
+        sel = np.flatnonzero(dk.nbytes > 0)
+        tix = dk.tix.astype(np.int64)
+        r0, r1 = dk.trow[sel], dk.trow[sel] + dk.tiles[sel]
+        ok = dk.slots.ndim == 2 and dk.slots.shape[1] == mio.DICT_SLOT and 256 <= len(dk.slots) <= mio.DICT_MAX_ENTRIES
+        ok = ok and not (dk.offsets[sel] % 16).any() and (2 * dk.units[sel] == dk.nbytes[sel]).all() and \
+            (dk.offsets[sel] + dk.nbytes[sel] <= dk.buffer.numel()).all() and (dk.tiles[sel] >= 1).all() and \
+            (len(sel) == 0 or int(r1.max()) < len(tix))
+        if ok and len(sel):
+            step = np.diff(tix, axis=0)
+            inner = np.ones(len(step), dtype=bool)
+            inner[r1[r1 < len(step)]] = False  # (from a split's closing row to the next split's first)
+            inner[:int(r0[0])] = False
+            inner[int(r1[-1]):] = False
+            ok = (tix[r0] == 0).all() and (tix[r1, 0] == dk.units[sel]).all() and \
+                (step[inner, 0] >= 1).all() and (step[inner, 0] <= mio.DICT_TILE_UNITS).all() and \
+                (step[inner, 1] >= 1).all() and (step[inner, 1] <= mio.DICT_TILE_BYTES).all()
+        if not ok:
+            raise ValueError("dictionary-coded split store: the tile index or the dictionary does not match the format")
+        d_slots = torch.from_numpy(np.ascontiguousarray(dk.slots)).to(self.device)
+        d_tix = torch.from_numpy(dk.tix.view(np.int32)).to(self.device)
+        self._dict_dev = (dk, d_slots, d_tix)
+        return d_slots, d_tix
+
     def _plan_unpack(self, ids: list[int], slot: int, bounds):
         """The packed half of a copy plan: the slot's device staging buffer for
         the packed bytes of the range, the unpack descriptors and code tables
         (uploaded here, once per cached plan), and per chunk the packed host ->
         staging copy, the raw host -> arena copies of its raw splits (more than
-        128 distinct byte values: never packed) and its descriptor range."""
+        128 distinct byte values: never packed) and its descriptor range.
+
+        With the dictionary-coded copy (:meth:`_ships_dict`) a split is in one
+        of three forms — dictionary where the store holds it so, else k-bit,
+        else raw; the staging buffer then has a second region for the code
+        units, and a chunk also carries its host -> staging copy of them
+        (``ddev`` / ``dhost``) and its range of the decoder's descriptors
+        (``dd0`` / ``dnd`` / ``dmax_t``; ``dict`` holds what the decoder
+        reads).  The k-bit copy of the store is laid out for all its splits, so
+        where a chunk mixes the forms its one k-bit copy, from its first to its
+        last k-bit split, also carries the k-bit bytes of the dictionary-coded
+        splits in between (and the staging region holds them); a chunk whose
+        splits are all of one form, the usual case, ships only that form."""
         st = self.splits
         pk = st.packed
+        dk = st.dict_packed if self._ships_dict() else None
         l0 = ids[0] - st.own[0]
         n = len(ids)
         poff, pby, kk = pk.offsets[l0:l0 + n], pk.nbytes[l0:l0 + n], pk.k[l0:l0 + n]
         a = st.region(ids[0], ids[0] + 1)[0]
         dst = st.offsets[ids[0]:ids[0] + n] - st.base - a
         size = st.offsets[ids[0] + 1:ids[0] + n + 1] - st.offsets[ids[0]:ids[0] + n]
+        isd = dk.nbytes[l0:l0 + n] > 0 if dk is not None else np.zeros(n, dtype=bool)
         p_a = int(poff[0])
         p_b = max(int((poff + pby).max()), p_a)
         need = max(p_b - p_a, 16)
+        d_base = need_d = d_a = 0
+        if dk is not None:
+            # the k-bit region spans only the splits that are shipped k-bit, from the first to the last
+            km = (kk < 8) & ~isd
+            p_a = int(poff[km].min()) if km.any() else p_a
+            p_b = int((poff + pby)[km].max()) if km.any() else p_a
+            need = max(p_b - p_a, 16)
+            dof, dby = dk.offsets[l0:l0 + n], dk.nbytes[l0:l0 + n]
+            if isd.any():
+                d_a = int(dof[isd].min())
+                need_d = int((dof + dby)[isd].max()) - d_a
+            d_base = (need + 15) & ~15
+            need = d_base + need_d
         stg = self._pack_staging[slot]
         if stg is None or stg.numel() < need:
             if stg is not None:
@@ -115,7 +180,7 @@ class StagingMixin:
                 self.copy_stream.synchronize()
             stg = self._pack_staging[slot] = torch.empty(need, dtype=torch.uint8, device=self.device)
             self._plans = {k: v for k, v in self._plans.items() if k[2] != slot}
-        packed = np.flatnonzero(kk < 8)
+        packed = np.flatnonzero((kk < 8) & ~isd)
         if (pby[packed] != (size[packed] + 15) // 16 * 2 * kk[packed]).any() or (poff % 16).any() or \
                 (poff[packed] + pby[packed] > pk.buffer.numel()).any():
             raise ValueError("packed split store: sizes or offsets do not match the split layout")
@@ -126,27 +191,55 @@ class StagingMixin:
         desc[:, 3] = kk[packed].astype(np.int64) | ((np.arange(len(packed), dtype=np.int64) * 128) << 32)
         tables = np.ascontiguousarray(pk.tables[l0:l0 + n][packed]).reshape(-1)
         first = np.searchsorted(packed, np.asarray(bounds))  # descriptor range of every chunk
+        dsel = np.flatnonzero(isd)
+        dfirst = np.searchsorted(dsel, np.asarray(bounds))
+        ddesc = np.zeros((max(len(dsel), 1), 4), dtype=np.int64)
+        if len(dsel):
+            g = l0 + dsel  # (the store's numbering)
+            if (dk.tix[dk.trow[g] + dk.tiles[g], 1] != size[dsel]).any() or (size[dsel] >= 1 << 32).any():
+                raise ValueError("dictionary-coded split store: a tile index does not match its split's size")
+            ddesc[:len(dsel), 0] = dof[dsel] - d_a
+            ddesc[:len(dsel), 1] = dst[dsel]
+            ddesc[:len(dsel), 2] = size[dsel] | (dk.units[g] << 32)
+            ddesc[:len(dsel), 3] = dk.trow[g] | (dk.tiles[g] << 32)
         chunks = []
         for i in range(len(bounds) - 1):
             b0, b1 = bounds[i], bounds[i + 1]
             ca = int(poff[b0]) - p_a
             cb = max(int((poff[b0:b1] + pby[b0:b1]).max()), int(poff[b0])) - p_a
+            if dk is not None:  # from the first to the last split of the chunk that is shipped k-bit
+                ks = packed[int(first[i]):int(first[i + 1])]
+                ca = int(poff[ks[0]]) - p_a if len(ks) else 0
+                cb = int((poff[ks] + pby[ks]).max()) - p_a if len(ks) else 0
             raw = []
-            for j in np.flatnonzero(kk[b0:b1] >= 8):  # (runs of raw splits are rare: one copy each)
+            for j in np.flatnonzero((kk[b0:b1] >= 8) & ~isd[b0:b1]):  # (runs of raw splits are rare: one copy each)
                 ra, rb = st.region(ids[0] + b0 + int(j), ids[0] + b0 + int(j) + 1)
                 raw.append((self.arenas[slot][ra - a:rb - a], st.buffer[ra:rb]))
             d0, d1 = int(first[i]), int(first[i + 1])
             chunks.append({"dev": stg[ca:cb], "host": pk.buffer[p_a + ca:p_a + cb], "raw": raw, "d0": d0,
                            "nd": d1 - d0, "max_n": int(desc[d0:d1, 2].max()) if d1 > d0 else 0})
+            if dk is not None:
+                e0, e1 = int(dfirst[i]), int(dfirst[i + 1])
+                ds = dsel[e0:e1]
+                da = int(dof[ds[0]]) - d_a if len(ds) else 0
+                db = int((dof[ds] + dby[ds]).max()) - d_a if len(ds) else 0
+                chunks[-1].update({"ddev": stg[d_base + da:d_base + db], "dhost": dk.buffer[d_a + da:d_a + db],
+                                   "dd0": e0, "dnd": e1 - e0,
+                                   "dmax_t": int(dk.tiles[l0 + ds].max()) if len(ds) else 0})
         dev = self.device
-        return {"staging": stg, "chunks": chunks, "slot": slot,
+        plan = {"staging": stg, "chunks": chunks, "slot": slot,
                 "desc": torch.from_numpy(desc).to(dev) if len(packed) else torch.zeros((1, 4), dtype=torch.int64,
                                                                                         device=dev),
                 "tables": torch.from_numpy(tables).to(dev) if len(packed) else torch.zeros(128, dtype=torch.uint8,
                                                                                             device=dev)}
+        if dk is not None:
+            d_slots, d_tix = self._dict_on_device(dk)
+            plan["dict"] = {"codes": stg[d_base:d_base + need_d], "desc": torch.from_numpy(ddesc).to(dev),
+                            "slots": d_slots, "tix": d_tix}
+        return plan
 
     def _plan_key(self, ids: list[int], slot: int, single: bool):
-        return (ids[0], len(ids), slot, single, self._ships_packed())
+        return (ids[0], len(ids), slot, single, 2 if self._ships_dict() else self._ships_packed())
 
     def _get_plan(self, ids: list[int], slot: int, single: bool = False):
         key = self._plan_key(ids, slot, single)
@@ -216,15 +309,26 @@ class StagingMixin:
         bytes (profiles/input_pack/README.md).  Stream order also settles the
         reuse of the staging buffer, which is one per arena slot and shared by
         the slot's plans: a later copy into it is queued behind every unpack
-        that reads it."""
+        that reads it.
+
+        A plan with the dictionary form (``pk["dict"]``) issues per chunk the
+        copy of its code units first, then the k-bit copy and the raw splits,
+        then at most one launch of each decoder."""
         from ..ops import _hip
         cs = self.copy_stream
         stg, arena, desc, tables = pk["staging"], self.arenas[pk["slot"]], pk["desc"], pk["tables"]
+        dc = pk.get("dict")
         for c, ev in zip(pk["chunks"], events):
+            if dc is not None and c["ddev"].numel():
+                _hip.call("mr_memcpy_async", _hip.ptr(c["ddev"]), _hip.ptr(c["dhost"]), c["ddev"].numel(), 1, sp)
             if c["dev"].numel():
                 _hip.call("mr_memcpy_async", _hip.ptr(c["dev"]), _hip.ptr(c["host"]), c["dev"].numel(), 1, sp)
             for dst, src in c["raw"]:
                 _hip.call("mr_memcpy_async", _hip.ptr(dst), _hip.ptr(src), dst.numel(), 1, sp)
+            if dc is not None and c["dnd"]:
+                _hip.call("mr_undict_splits", _hip.ptr(dc["codes"]), dc["codes"].numel(), _hip.ptr(arena),
+                          arena.numel(), ctypes.c_void_p(dc["desc"].data_ptr() + 32 * c["dd0"]), c["dnd"], c["dmax_t"],
+                          _hip.ptr(dc["tix"]), dc["tix"].shape[0], _hip.ptr(dc["slots"]), dc["slots"].shape[0], sp)
             if c["nd"]:
                 _hip.call("mr_unpack_splits", _hip.ptr(stg), stg.numel(), _hip.ptr(arena), arena.numel(),
                           ctypes.c_void_p(desc.data_ptr() + 32 * c["d0"]), c["nd"], c["max_n"], _hip.ptr(tables),

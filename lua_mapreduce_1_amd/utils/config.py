@@ -104,6 +104,12 @@ class Tunables:
                              "of its alphabet, csrc/host/pack.cpp) made once when loading finishes; iterations "
                              "ship that copy over PCIe and a kernel restores the bytes in the arena (csrc/hip/"
                              "unpack.hip).  Off: raw bytes are shipped, no packed buffer, no extra launches")
+    pack_dict: bool = _knob("MR_PACK_DICT", True,
+                            "with MR_PACK_INPUT: the store also keeps a dictionary-coded copy (whole tokens as 16-bit "
+                            "code units against one dictionary of the store's tokens, csrc/host/dictpack.cpp); a "
+                            "split is shipped in that form where it is the smallest, the dictionary stays in HBM "
+                            "and a kernel restores the bytes in the arena (csrc/hip/undict.hip).  Off: exactly "
+                            "the MR_PACK_INPUT behaviour, no dictionary copy")
     sdma_min_mb: float = _knob("MR_SDMA_MIN_MB", 8.0,
                                "result downloads of at least this many MiB go over the SDMA copy engines (ROCr copy "
                                "API, csrc/hip/sdma.hip) after the tail's kernels, not as a runtime blit kernel on "

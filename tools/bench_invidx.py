@@ -97,6 +97,10 @@ def main() -> int:
                     help="check the WHOLE index against a host oracle built from the corpus bytes: every word's "
                          "number of distinct lines and the sum of its line ids (plus a 1/8-corpus exact diff)")
     ap.add_argument("--vocab-log2", type=int, default=0, help="vocabulary table capacity 2^k (0 = the plane's default)")
+    ap.add_argument("--pack-dict", action="store_true",
+                    help="also make and ship the dictionary-coded copy of the splits (MR_PACK_DICT).  Off here: with "
+                         "k-bit input the step is already set by this job's kernels, and the dictionary decoder takes "
+                         "compute units from them (4.78 -> 4.97-5.16 ms, profiles/input_dict/README.md)")
     args = ap.parse_args()
     rank, world, device = D.init_from_env()
     cdir = corpus_dir(args.seed, corpus.EUROPARL_LINES, corpus.EUROPARL_WORDS)
@@ -105,7 +109,7 @@ def main() -> int:
     D.barrier(device=device)
     off = np.load(os.path.join(cdir, "off.npy"))
     store = SplitStore.from_blob(os.path.join(cdir, "blob.bin"), off, rank, world, pin=device.type == "cuda")
-    store.finish_loading()
+    store.finish_loading(pack_dict=None if args.pack_dict else False)
     params = dict(taskfn=M, mapfn=M, partitionfn=M, reducefn=M, finalfn=M,
                   init_args={"nsplits": len(store), "num_reducers": args.reducers, "quiet": True})
     if args.vocab_log2:

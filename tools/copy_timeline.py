@@ -5,7 +5,7 @@ H2D rate, the copy engine's busy time per step and the gaps between
 consecutive copies.  The brackets cost a little host time per copy, so the
 step time printed here is not the headline's.
 
-    python tools/copy_timeline.py [--steps 20 --warmup 5]      (MR_PACK_INPUT=0|1)
+    python tools/copy_timeline.py [--steps 20 --warmup 5]      (MR_PACK_INPUT=0|1, MR_PACK_DICT=0|1)
 """
 import argparse
 import gc
@@ -77,7 +77,7 @@ def main() -> int:
     gaps = [spans[i + 1][0] - spans[i][1] for i in range(len(spans) - 1)]
     big = [(b - a, n) for a, b, n in spans if n >= 32 << 20]
     print(json.dumps({
-        "pack_input": eng._ships_packed(), "steps": args.steps, "ms_per_step_with_brackets": ms,
+        "pack_input": eng._ships_packed(), "pack_dict": eng._ships_dict(), "steps": args.steps, "ms_per_step_with_brackets": ms,
         "copies": len(spans), "h2d_bytes_per_step": nbytes / args.steps, "copy_busy_ms_per_step": busy / args.steps,
         "h2d_GBps_copies_of_32MiB_up": sum(n for _, n in big) / max(sum(t for t, _ in big), 1e-9) / 1e6,
         "first_copy_to_last_copy_end_ms": spans[-1][1] - spans[0][0],

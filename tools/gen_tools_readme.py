@@ -19,6 +19,16 @@ file's docstring or header comment by `tools/gen_tools_readme.py`.
 |---|---|
 """
 
+TAIL = """
+## Input forms on the host -> HBM link
+
+`pack_bytes.py` and `copy_timeline.py` report on the forms a pinned `SplitStore` keeps for re-staging (raw, k-bit
+codes, dictionary codes). The formats, the knobs (`MR_PACK_INPUT`, `MR_PACK_DICT`) and what each form costs are in
+`docs/GUIDE.md` (the `MR_PACK_INPUT` and `MR_PACK_DICT` entries); the measurements are in
+`profiles/input_pack/README.md` and `profiles/input_dict/README.md`. `bench_invidx.py` and the bigram job of
+`bench_generic.py` are not bound by the link and ship k-bit codes unless run with `--pack-dict`.
+"""
+
 
 def describe(path: str) -> str:
     text = open(path, encoding="utf-8", errors="replace").read()
@@ -51,7 +61,7 @@ def main() -> None:
             if os.path.isfile(p) and name.endswith((".py", ".sh", ".hip")) and name != "README.md":
                 rows.append(f"| `{os.path.join(sub, name) if sub else name}` | {describe(p).replace('|', '/')} |")
     with open(os.path.join(HERE, "README.md"), "w") as f:
-        f.write(HEAD + "\n".join(rows) + "\n")
+        f.write(HEAD + "\n".join(rows) + "\n" + TAIL)
 
 
 if __name__ == "__main__":

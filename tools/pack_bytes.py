@@ -1,5 +1,7 @@
-"""Raw and bit-packed size of the benchmark corpus and the histogram of the
-code widths of its splits (csrc/host/pack.cpp); CPU only.
+"""Raw, bit-packed and dictionary-coded size of the benchmark corpus: the
+histogram of the code widths of its splits (csrc/host/pack.cpp), and the
+dictionary form's bytes, entries, dictionary size and pack time (csrc/host/
+dictpack.cpp); CPU only.
 
     python tools/pack_bytes.py [--threads 8]
 """
@@ -29,15 +31,24 @@ def main() -> int:
                                  threads=args.threads)
     store.finish_loading(pack=False)
     t0 = time.perf_counter()
-    store.finish_loading(pack=True)
+    store.finish_loading(pack=True, pack_dict=False)
     dt = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    store.finish_loading(pack=True, pack_dict=True)
+    ddt = time.perf_counter() - t0
+    dk = store.dict_packed
     pk = store.packed
     raw = int(store.buffer.numel())
     hist = collections.Counter(int(k) for k in pk.k)
     odd = [i for i, k in enumerate(pk.k) if k != 6]
     print(json.dumps({"splits": len(store), "raw_bytes": raw, "packed_bytes": int(pk.buffer.numel()),
                       "ratio": pk.buffer.numel() / raw, "width_histogram": dict(sorted(hist.items())),
-                      "splits_not_6_bits": odd, "pack_seconds": dt, "threads": args.threads}))
+                      "splits_not_6_bits": odd, "pack_seconds": dt, "threads": args.threads,
+                      "dict_bytes": int(dk.buffer.numel()), "dict_ratio": dk.buffer.numel() / raw,
+                      "dict_splits": int((dk.nbytes > 0).sum()), "dict_entries": int(len(dk.slots)),
+                      "dict_one_unit_entries": int(min(len(dk.slots), 0xC000)),
+                      "dictionary_bytes": int(dk.slots.nbytes), "tile_index_bytes": int(dk.tix.nbytes),
+                      "dict_pack_seconds": ddt, "dict_threads": max(args.threads, 16)}))
     return 0
 
 

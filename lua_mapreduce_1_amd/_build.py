@@ -34,6 +34,10 @@ HIP_LIB = os.path.join(LIBDIR, "libmrhip.so")
 COORD_LIB = os.path.join(LIBDIR, "libmrcoord.so")
 HOST_LIB = os.path.join(LIBDIR, "libmrhost.so")
 
+# per-file compiler flags: the k-means kernel's fp32 error bounds assume scalar
+# (unpacked) fp32 arithmetic around its MFMA chains
+HIP_EXTRA = {"kmeans.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
 
 def _newer(target: str, sources: list[str]) -> bool:
     if not os.path.exists(target):
@@ -66,7 +70,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
         if not force and not _newer(o, [s] + headers):
             continue
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-Wall",
-               "-Wno-unused-function", "-I", srcdir, "-c", s, "-o", o]
+               "-Wno-unused-function", "-I", srcdir, "-c", s, "-o", o] + HIP_EXTRA.get(os.path.basename(s), [])
         if verbose:
             print(" ".join(cmd))
         _run(cmd)

@@ -1,0 +1,213 @@
+"""Lloyd's k-means as an iterative MapReduce job on the tensor plane.
+
+One module provides every function (pass it as taskfn, mapfn, partitionfn,
+reducefn and finalfn) and runs in SPMD form only, through ``execute_spmd.py`` /
+``lua_mapreduce_1_amd.spmd``.  A server/worker form would need the model in a
+persistent table and the blob store, as examples/DigitsMLP has; that is out of
+scope here.
+
+* ``init(args)``: ``files`` — raw little-endian fp32 ``[n_i, dim]`` row-major
+  files, one per map job, or ``"synthetic"`` (``make_points(seed, n, dim, k,
+  nsplits)``, with ``n`` and ``nsplits`` in the args) — ``k``, ``dim``,
+  ``max_iters`` (20), ``tol`` (1e-4: stop when the largest squared centroid
+  shift is <= tol), ``seed``, and optionally ``centroids`` (array or raw fp32
+  file).  Without ``centroids`` every rank picks the same k distinct rows,
+  ``default_rng(seed).choice(n_total, k, replace=False)``, and reads just those
+  rows through a memmap.
+* map: one job per file.  The job's points go to the device once and stay
+  there across iterations; ``ops.kmeans.step`` (one fused MFMA launch on a
+  GPU) assigns them to the replicated centroids and its partial sums are
+  ADDED into the tensor plane's accumulators (a rank may run several jobs).
+* the plane is fp32: ``SUMS`` [k*dim] carries fp32 of the float64 partial
+  sums, ``COST`` [1] the cost, and ``COUNTS`` [2k] every cluster's count as two
+  exact fp32 words, ``c & 0xFFFFF`` and ``c >> 20`` (exact for W <= 16 ranks
+  and 2^44 points); ``device_finalfn`` rejoins them in int64.
+* final (every rank): centroid = sum / count, an empty cluster keeps its
+  centroid; ``HISTORY`` gets ``{iter, cost, shift, empty}``; ``"loop"`` until
+  the shift is <= tol or ``max_iters`` is reached.  Afterwards ``CENTROIDS``
+  (device tensor) and ``predict(X)`` (``ops.kmeans.assign``) serve the model.
+* ``naive(splits, ...)``: plain float64 numpy Lloyd's with the same init, tie
+  rule, empty-cluster rule and stopping rule.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from lua_mapreduce_1_amd.ops import io as _io
+from lua_mapreduce_1_amd.ops import kmeans as K
+
+NUM_REDUCERS = 10
+KEYS = ("SUMS", "COUNTS", "COST")
+_LO_BITS = 20
+
+device_reduce = "tensor_sum"
+spmd_replicated_taskfn = True
+
+HISTORY: list = []
+CENTROIDS = None
+_st: dict = {}
+
+
+def make_points(seed: int, n: int, dim: int, k: int, nsplits: int) -> list:
+    """``nsplits`` fp32 arrays [n_i, dim]: n points around k Gaussian blobs
+    (centres N(0, 10^2), unit spread), in random order."""
+    rng = np.random.default_rng(seed)
+    centres = rng.normal(0.0, 10.0, (k, dim))
+    pts = centres[rng.integers(0, k, n)] + rng.normal(0.0, 1.0, (n, dim))
+    return [np.ascontiguousarray(s, dtype=np.float32) for s in np.array_split(pts, nsplits)]
+
+
+def _rows(src, dim: int) -> np.ndarray:
+    """A split as a [n_i, dim] fp32 array (a memmap of a file)."""
+    return src if isinstance(src, np.ndarray) else np.memmap(src, dtype="<f4", mode="r").reshape(-1, dim)
+
+
+def initial_centroids(splits, k: int, dim: int, seed: int) -> np.ndarray:
+    """k distinct rows of the concatenated splits, the same on every rank."""
+    sizes = [_rows(s, dim).shape[0] for s in splits]
+    pick = np.random.default_rng(seed).choice(int(sum(sizes)), k, replace=False)
+    ends = np.cumsum(sizes)
+    out = np.empty((k, dim), dtype=np.float32)
+    for j, r in enumerate(pick):
+        s = int(np.searchsorted(ends, r, side="right"))
+        out[j] = _rows(splits[s], dim)[r - (ends[s] - sizes[s])]
+    return out
+
+
+def split_counts(c: torch.Tensor) -> torch.Tensor:
+    """int64 counts [k] -> fp32 [2k]: the low 20 bits, then the rest."""
+    return torch.cat([(c & ((1 << _LO_BITS) - 1)), (c >> _LO_BITS)]).to(torch.float32)
+
+
+def rejoin_counts(t: torch.Tensor) -> torch.Tensor:
+    """fp32 [2k] (sums of split words) -> int64 counts [k]."""
+    k = t.numel() // 2
+    w = t.to(torch.int64)
+    return w[:k] + (w[k:] << _LO_BITS)
+
+
+def init(args):
+    global HISTORY, CENTROIDS
+    a = dict(args or {})
+    _st.clear()
+    HISTORY = []
+    CENTROIDS = None
+    k, dim = int(a["k"]), int(a["dim"])
+    files = a.get("files", "synthetic")
+    seed = int(a.get("seed", 0))
+    if files == "synthetic":
+        splits = make_points(seed, int(a.get("n", 20000)), dim, k, int(a.get("nsplits", 4)))
+    else:
+        splits = [files] if isinstance(files, str) else list(files)
+    c = a.get("centroids")
+    if c is None:
+        c0 = initial_centroids(splits, k, dim, seed)
+    elif isinstance(c, str):
+        c0 = np.fromfile(c, dtype="<f4").reshape(k, dim)
+    else:
+        c0 = np.asarray(c, dtype=np.float32).reshape(k, dim)
+    _st.update(k=k, dim=dim, splits=splits, c0=np.ascontiguousarray(c0, dtype=np.float32), points={},
+               max_iters=int(a.get("max_iters", 20)), tol=float(a.get("tol", 1e-4)))
+
+
+def taskfn(emit):
+    for j, s in enumerate(_st["splits"]):
+        emit(j + 1, j if isinstance(s, np.ndarray) else s)
+
+
+def device_tensor_layout() -> dict:
+    return {"SUMS": _st["k"] * _st["dim"], "COUNTS": 2 * _st["k"], "COST": 1}
+
+
+def _centroids(device) -> torch.Tensor:
+    global CENTROIDS
+    if CENTROIDS is None:
+        CENTROIDS = torch.from_numpy(_st["c0"]).to(device)
+    return CENTROIDS
+
+
+def _points(key, value, device) -> torch.Tensor:
+    x = _st["points"].get(key)
+    if x is None:
+        if isinstance(value, str):
+            x = _io.load_file(value, device).view(torch.float32).view(-1, _st["dim"])
+        else:
+            x = torch.from_numpy(_st["splits"][int(value)]).to(device)
+        _st["points"][key] = x
+    return x
+
+
+def device_mapfn(key, value, emit):
+    """Assign the job's points (device-resident after the first iteration) to
+    the replicated centroids and add the partial sums into the plane."""
+    dev = emit.device
+    sums, counts, cost, _ = K.step(_points(key, value, dev), _centroids(dev))
+    emit.accumulator("SUMS").add_(sums.reshape(-1).to(torch.float32))
+    cw = emit.accumulator("COUNTS")
+    cw.copy_(split_counts(rejoin_counts(cw) + counts))  # add, then renormalise the two words
+    emit.accumulator("COST").add_(cost.to(torch.float32))
+
+
+def partitionfn(key):
+    return sum(key.encode()) % NUM_REDUCERS
+
+
+def reducefn(key, values, emit):
+    emit(sum(np.asarray(v, dtype=np.float64) for v in values))
+
+
+def device_finalfn(res, engine):
+    """Every rank: move the centroids, record the iteration, decide to loop."""
+    global CENTROIDS
+    k, dim = _st["k"], _st["dim"]
+    old = _centroids(engine.device)
+    counts = rejoin_counts(res.tensors["COUNTS"])
+    sums = res.tensors["SUMS"].view(k, dim).to(torch.float64)
+    live = counts > 0
+    new = torch.where(live[:, None], sums / counts.clamp(min=1)[:, None].to(torch.float64), old.to(torch.float64))
+    shift = float(((new - old.to(torch.float64)) ** 2).sum(1).max())
+    CENTROIDS = new.to(torch.float32).contiguous()
+    HISTORY.append({"iter": len(HISTORY) + 1, "cost": float(res.tensors["COST"][0]), "shift": shift,
+                    "empty": int((~live).sum())})
+    if engine.rank == 0 and engine.verbose:
+        print("# kmeans iter %(iter)d cost %(cost).6g shift %(shift).3g empty %(empty)d" % HISTORY[-1], flush=True)
+    return "loop" if shift > _st["tol"] and len(HISTORY) < _st["max_iters"] else True
+
+
+def finalfn(pairs):
+    raise RuntimeError("examples/KMeans runs in SPMD form only (device_finalfn)")
+
+
+def mapfn(key, value, emit):
+    raise RuntimeError("examples/KMeans runs in SPMD form only (device_mapfn)")
+
+
+def predict(X) -> torch.Tensor:
+    """int32 labels of the rows of X under the fitted centroids."""
+    x = torch.as_tensor(np.ascontiguousarray(X, dtype=np.float32) if isinstance(X, np.ndarray) else X)
+    return K.assign(x.to(CENTROIDS.device).contiguous(), CENTROIDS)
+
+
+def naive(splits, k: int, dim: int, max_iters: int = 20, tol: float = 1e-4, seed: int = 0, centroids=None) -> dict:
+    """Plain float64 numpy Lloyd's: the oracle of the job above."""
+    X = np.concatenate([np.asarray(_rows(s, dim)) for s in splits]).astype(np.float64)
+    C = (initial_centroids(splits, k, dim, seed) if centroids is None
+         else np.asarray(centroids, dtype=np.float32).reshape(k, dim)).astype(np.float64)
+    history = []
+    while True:
+        lab = np.empty(len(X), dtype=np.int64)
+        cost = 0.0
+        for i in range(0, len(X), 8192):
+            D = ((X[i:i + 8192, None, :] - C[None]) ** 2).sum(-1)
+            lab[i:i + 8192] = D.argmin(1)  # first minimum: the lowest index
+            cost += float(D.min(1).sum())
+        sums = np.zeros((k, dim))
+        np.add.at(sums, lab, X)
+        counts = np.bincount(lab, minlength=k)
+        new = np.where(counts[:, None] > 0, sums / np.maximum(counts, 1)[:, None], C)
+        shift = float(((new - C) ** 2).sum(1).max())
+        C = new
+        history.append({"iter": len(history) + 1, "cost": cost, "shift": shift, "empty": int((counts == 0).sum())})
+        if not (shift > tol and len(history) < max_iters):
+            return {"centroids": C, "history": history}

@@ -4,3 +4,4 @@ from .primitives import (HashTable, tokenize, key_meta, key_bytes_list, exclusiv
                          sort_keys, sort_keys_checked, sort_error, debug_sort_fail, sort_by_partition_key, bincount, reduce_by_key, next_pow2,
                          exact_key_perm, gather_aos4)
 from . import keys  # noqa: F401
+from . import kmeans  # noqa: F401

@@ -1,0 +1,133 @@
+"""The fused k-means map step (ops.kmeans.step, csrc/hip/kmeans.hip) against the
+plain torch chain a user would write in device_mapfn (``X @ C.T`` + ``argmin`` +
+``index_add_``, in row blocks of 2^20 so the n x k scores fit), on the same
+tensors in the same process, alternating: n = 2^24 points, d in {16, 64, 128},
+k in {16, 256, 1024}.  One step on a sample is validated against the CPU
+specification first (labels under the margin rule, counts, sums, cost); a wrong
+answer exits non-zero.  Times are medians of device-event timings after
+warm-up; each shape also gets its two floors, 2 n k d FLOP at the fp32 MFMA
+peak and 4 n d bytes at the HBM peak (datasheet: 157.3 TFLOP/s, 8 TB/s).
+
+    python tools/bench_kmeans.py [--n 16777216] [--steps 5] [--warmup 2] [--shapes 16x16,64x256]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from lua_mapreduce_1_amd.ops import kmeans as K  # noqa: E402
+
+PEAK_FLOPS = 157.3e12  # MI355X fp32 matrix
+PEAK_BYTES = 8.0e12    # MI355X HBM3E
+U = 2.0 ** -24
+
+
+def make(n, d, k, dev):
+    g = torch.Generator(device=dev).manual_seed(1)
+    C = torch.randn(k, d, device=dev, generator=g) * 10
+    X = torch.empty(n, d, device=dev)
+    for i in range(0, n, 1 << 20):
+        m = min(1 << 20, n - i)
+        X[i:i + m] = C[torch.randint(0, k, (m,), device=dev, generator=g)] + torch.randn(m, d, device=dev, generator=g)
+    return X, C
+
+
+def torch_chain(X, C):
+    k, d = C.shape
+    sums = torch.zeros(k, d, device=X.device)
+    counts = torch.zeros(k, dtype=torch.int64, device=X.device)
+    cn = (C * C).sum(1)
+    for i in range(0, X.shape[0], 1 << 20):
+        x = X[i:i + (1 << 20)]
+        lab = (cn - 2 * (x @ C.T)).argmin(1)
+        sums.index_add_(0, lab, x)
+        counts += torch.bincount(lab, minlength=k)
+    return sums, counts
+
+
+def validate(X, C, rows=4096):
+    """One kernel step on a strided sample against the CPU specification."""
+    n, d = X.shape
+    xs = X[::max(1, n // rows)][:rows].contiguous()
+    sums, counts, cost, lab = K.step(xs, C, labels=True)
+    s64, c64, q64, l64 = K.step(xs.cpu(), C.cpu(), labels=True)
+    X64, C64 = xs.cpu().double(), C.cpu().double()
+    D = torch.cdist(X64, C64) ** 2
+    g = (d + 2) * U / (1 - (d + 2) * U)
+    E = 2 * g * (X64.norm(dim=1) + C64.norm(dim=1).max()) ** 2
+    lab = lab.cpu().long()
+    best = D.min(1).values
+    ok = bool((D.gather(1, lab[:, None])[:, 0] <= best + E + 1e-9 * best).all())  # (1e-9: cdist's own rounding)
+    two = D.topk(min(2, D.shape[1]), dim=1, largest=False).values
+    clear = (two[:, -1] - two[:, 0] > E + 1e-9 * best) if D.shape[1] > 1 else torch.ones(len(lab), dtype=torch.bool)
+    ok &= bool((lab[clear] == l64.long()[clear]).all())
+    ok &= bool((counts.cpu() == torch.bincount(lab, minlength=C.shape[0])).all())
+    want = torch.zeros_like(s64).index_add_(0, lab, X64)
+    mass = torch.zeros_like(s64).index_add_(0, lab, X64.abs())
+    nj = counts.cpu().double()
+    ok &= bool(((sums.cpu() - want).abs() <= 2 * (nj * U / (1 - nj * U))[:, None] * mass).all())
+    ok &= bool(abs(float(cost.cpu()) - float(q64)) <= float((E + g * X64.norm(dim=1) ** 2).sum()) + 1e-6 * float(q64))
+    return ok
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1 << 24)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--shapes", default=",".join(f"{d}x{k}" for d in (16, 64, 128) for k in (16, 256, 1024)))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_kmeans needs a GPU: nothing is measured without one")
+    dev = torch.device("cuda", 0)
+    box = torch.cuda.get_device_name(0)
+    bad = 0
+    for shape in a.shapes.split(","):
+        d, k = (int(v) for v in shape.split("x"))
+        X, C = make(a.n, d, k, dev)
+        valid = validate(X, C)
+        sums = torch.zeros(k, d, dtype=torch.float64, device=dev)
+        counts = torch.zeros(k, dtype=torch.int64, device=dev)
+        cost = torch.zeros(1, dtype=torch.float64, device=dev)
+        tk, tt = [], []
+        for _ in range(a.steps):  # alternate the two, one timed call each per round
+            tk += timed(lambda: K.step(X, C, sums, counts, cost), 1, a.warmup if not tk else 0)
+            tt += timed(lambda: torch_chain(X, C), 1, a.warmup if not tt else 0)
+        _s, tcounts = torch_chain(X, C)
+        calls = a.steps + a.warmup
+        valid &= int(counts.sum()) == calls * a.n
+        # the two paths may split near-ties differently: counts agree to within a 1e-3 share
+        valid &= float((counts.double() / calls - tcounts.double()).abs().sum()) <= 1e-3 * a.n
+        ms_k, ms_t = statistics.median(tk), statistics.median(tt)
+        f_flop, f_byte = 2.0 * a.n * k * d / PEAK_FLOPS * 1e3, 4.0 * a.n * d / PEAK_BYTES * 1e3
+        print(json.dumps({"box": box, "n": a.n, "d": d, "k": k, "valid": bool(valid), "kernel_ms": round(ms_k, 3),
+                          "kernel_ms_all": [round(t, 3) for t in tk], "torch_ms": round(ms_t, 3),
+                          "torch_over_kernel": round(ms_t / ms_k, 2), "mfma_floor_ms": round(f_flop, 3),
+                          "hbm_floor_ms": round(f_byte, 3), "mfma_fraction": round(f_flop / ms_k, 3),
+                          "hbm_fraction": round(f_byte / ms_k, 3)}), flush=True)
+        bad += not valid
+        del X, C
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()

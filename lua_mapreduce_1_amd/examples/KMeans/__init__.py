@@ -13,7 +13,12 @@ scope here.
   shift is <= tol), ``seed``, and optionally ``centroids`` (array or raw fp32
   file).  Without ``centroids`` every rank picks the same k distinct rows,
   ``default_rng(seed).choice(n_total, k, replace=False)``, and reads just those
-  rows through a memmap.
+  rows through a memmap.  ``point_dtype`` is ``"fp32"`` (default) or
+  ``"bf16"``: the files are then raw little-endian bf16 rows, ``"synthetic"``
+  points are rounded to bf16 once, the step runs on the 16-bit matrix cores
+  against ``terms`` (3) bf16 pieces of every centroid (ops/kmeans.py), and the
+  centroids stay fp32.  numpy has no bf16: on the host such rows are
+  ``uint16`` and are widened by a 16-bit shift where values are needed.
 * map: one job per file.  The job's points go to the device once and stay
   there across iterations; ``ops.kmeans.step`` (one fused MFMA launch on a
   GPU) assigns them to the replicated centroids and its partial sums are
@@ -58,20 +63,38 @@ def make_points(seed: int, n: int, dim: int, k: int, nsplits: int) -> list:
     return [np.ascontiguousarray(s, dtype=np.float32) for s in np.array_split(pts, nsplits)]
 
 
-def _rows(src, dim: int) -> np.ndarray:
-    """A split as a [n_i, dim] fp32 array (a memmap of a file)."""
-    return src if isinstance(src, np.ndarray) else np.memmap(src, dtype="<f4", mode="r").reshape(-1, dim)
+def to_bf16(a: np.ndarray) -> np.ndarray:
+    """fp32 array -> its bf16 round-to-nearest-even, as uint16."""
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.bfloat16).view(torch.int16).numpy() \
+        .view(np.uint16)
 
 
-def initial_centroids(splits, k: int, dim: int, seed: int) -> np.ndarray:
+def widen(a: np.ndarray) -> np.ndarray:
+    """bf16 rows held as uint16 -> the same values in fp32 (exact)."""
+    return (np.asarray(a).astype(np.uint32) << 16).view(np.float32)
+
+
+def _rows(src, dim: int, point_dtype: str = "fp32") -> np.ndarray:
+    """A split as a [n_i, dim] array (a memmap of a file): fp32, or uint16 for bf16 points."""
+    if isinstance(src, np.ndarray):
+        return src
+    return np.memmap(src, dtype="<u2" if point_dtype == "bf16" else "<f4", mode="r").reshape(-1, dim)
+
+
+def _values(rows: np.ndarray) -> np.ndarray:
+    return widen(rows) if rows.dtype == np.uint16 else rows
+
+
+def initial_centroids(splits, k: int, dim: int, seed: int, point_dtype: str = "fp32") -> np.ndarray:
     """k distinct rows of the concatenated splits, the same on every rank."""
-    sizes = [_rows(s, dim).shape[0] for s in splits]
+    splits = [_rows(s, dim, point_dtype) for s in splits]
+    sizes = [s.shape[0] for s in splits]
     pick = np.random.default_rng(seed).choice(int(sum(sizes)), k, replace=False)
     ends = np.cumsum(sizes)
     out = np.empty((k, dim), dtype=np.float32)
     for j, r in enumerate(pick):
         s = int(np.searchsorted(ends, r, side="right"))
-        out[j] = _rows(splits[s], dim)[r - (ends[s] - sizes[s])]
+        out[j] = _values(splits[s][r - (ends[s] - sizes[s])])
     return out
 
 
@@ -96,19 +119,24 @@ def init(args):
     k, dim = int(a["k"]), int(a["dim"])
     files = a.get("files", "synthetic")
     seed = int(a.get("seed", 0))
+    dt, terms = a.get("point_dtype", "fp32"), int(a.get("terms", 3))
+    if dt not in ("fp32", "bf16"):
+        raise ValueError(f"KMeans: point_dtype is 'fp32' or 'bf16' (got {dt!r})")
     if files == "synthetic":
         splits = make_points(seed, int(a.get("n", 20000)), dim, k, int(a.get("nsplits", 4)))
+        if dt == "bf16":
+            splits = [to_bf16(s) for s in splits]
     else:
         splits = [files] if isinstance(files, str) else list(files)
     c = a.get("centroids")
     if c is None:
-        c0 = initial_centroids(splits, k, dim, seed)
+        c0 = initial_centroids(splits, k, dim, seed, dt)
     elif isinstance(c, str):
         c0 = np.fromfile(c, dtype="<f4").reshape(k, dim)
     else:
         c0 = np.asarray(c, dtype=np.float32).reshape(k, dim)
     _st.update(k=k, dim=dim, splits=splits, c0=np.ascontiguousarray(c0, dtype=np.float32), points={},
-               max_iters=int(a.get("max_iters", 20)), tol=float(a.get("tol", 1e-4)))
+               max_iters=int(a.get("max_iters", 20)), tol=float(a.get("tol", 1e-4)), bf16=dt == "bf16", terms=terms)
 
 
 def taskfn(emit):
@@ -127,13 +155,24 @@ def _centroids(device) -> torch.Tensor:
     return CENTROIDS
 
 
+def _tdtype():
+    return torch.bfloat16 if _st["bf16"] else torch.float32
+
+
+def _tensor(rows: np.ndarray) -> torch.Tensor:
+    """A host array of points as a tensor of the job's point dtype (uint16 rows are bf16 bits)."""
+    if rows.dtype == np.uint16:
+        return torch.from_numpy(np.ascontiguousarray(rows).view(np.int16)).view(torch.bfloat16)
+    return torch.from_numpy(np.ascontiguousarray(rows, dtype=np.float32)).to(_tdtype())
+
+
 def _points(key, value, device) -> torch.Tensor:
     x = _st["points"].get(key)
     if x is None:
         if isinstance(value, str):
-            x = _io.load_file(value, device).view(torch.float32).view(-1, _st["dim"])
+            x = _io.load_file(value, device).view(_tdtype()).view(-1, _st["dim"])
         else:
-            x = torch.from_numpy(_st["splits"][int(value)]).to(device)
+            x = _tensor(_st["splits"][int(value)]).to(device)
         _st["points"][key] = x
     return x
 
@@ -142,7 +181,7 @@ def device_mapfn(key, value, emit):
     """Assign the job's points (device-resident after the first iteration) to
     the replicated centroids and add the partial sums into the plane."""
     dev = emit.device
-    sums, counts, cost, _ = K.step(_points(key, value, dev), _centroids(dev))
+    sums, counts, cost, _ = K.step(_points(key, value, dev), _centroids(dev), terms=_st["terms"])
     emit.accumulator("SUMS").add_(sums.reshape(-1).to(torch.float32))
     cw = emit.accumulator("COUNTS")
     cw.copy_(split_counts(rejoin_counts(cw) + counts))  # add, then renormalise the two words
@@ -185,14 +224,16 @@ def mapfn(key, value, emit):
 
 def predict(X) -> torch.Tensor:
     """int32 labels of the rows of X under the fitted centroids."""
-    x = torch.as_tensor(np.ascontiguousarray(X, dtype=np.float32) if isinstance(X, np.ndarray) else X)
-    return K.assign(x.to(CENTROIDS.device).contiguous(), CENTROIDS)
+    x = _tensor(X) if isinstance(X, np.ndarray) else torch.as_tensor(X).to(_tdtype())
+    return K.assign(x.to(CENTROIDS.device).contiguous(), CENTROIDS, terms=_st["terms"])
 
 
-def naive(splits, k: int, dim: int, max_iters: int = 20, tol: float = 1e-4, seed: int = 0, centroids=None) -> dict:
-    """Plain float64 numpy Lloyd's: the oracle of the job above."""
-    X = np.concatenate([np.asarray(_rows(s, dim)) for s in splits]).astype(np.float64)
-    C = (initial_centroids(splits, k, dim, seed) if centroids is None
+def naive(splits, k: int, dim: int, max_iters: int = 20, tol: float = 1e-4, seed: int = 0, centroids=None,
+          point_dtype: str = "fp32") -> dict:
+    """Plain float64 numpy Lloyd's: the oracle of the job above (bf16 points:
+    uint16 rows or bf16 files, i.e. the rounded points the job itself sees)."""
+    X = np.concatenate([_values(np.asarray(_rows(s, dim, point_dtype))) for s in splits]).astype(np.float64)
+    C = (initial_centroids(splits, k, dim, seed, point_dtype) if centroids is None
          else np.asarray(centroids, dtype=np.float32).reshape(k, dim)).astype(np.float64)
     history = []
     while True:

@@ -65,6 +65,9 @@ _SIGS = {
     "mr_mlp_param_count": [_i32, _i32, _i32],
     "mr_kmeans_step": [_p, _p, ctypes.c_longlong, _i32, _i32, _p, _p, _p, _p, _p],
     "mr_kmeans_lds_limit": [_i32],
+    "mr_kmeans_bf16_step": [_p, _p, ctypes.c_longlong, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p],
+    "mr_kmeans_bf16_workspace_bytes": [_i32, _i32, _i32],
+    "mr_kmeans_bf16_lds_limit": [_i32],
     "mr_count_newlines": [_p, _u64, _u64, _p, _p, _p],
     "mr_ii_map": [_p, _u64, _u64, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _u64, _u32, _p, _p, _u64, _p, _p],
     "mr_ii_advance": [_p, _p, _p],

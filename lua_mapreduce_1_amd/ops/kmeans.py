@@ -1,16 +1,19 @@
 """The map step of Lloyd's k-means: nearest-centroid assignment and the
 per-cluster partial sums in ONE launch (csrc/hip/kmeans.hip: distances on the
 fp32 matrix cores, argmin in registers, sums combined in LDS; the n x k
-distance matrix never exists).
+distance matrix never exists).  bf16 points run on the 16-bit matrix cores
+against fp32 centroids split into ``terms`` bf16 pieces
+(csrc/hip/kmeans_bf16.hip: a small prologue launch splits, then the same plan).
 
 ``step(X, C)`` assigns every row of ``X`` [n, d] to its nearest row of ``C``
 [k, d] and adds, into float64 ``sums`` [k, d], int64 ``counts`` [k] and float64
 ``cost`` [1], the members' coordinate sums, their number and the sum of squared
 distances.  ``assign(X, C)`` is the labels-only mode of the same kernel.
 
-Supported: contiguous fp32 ``X`` and ``C`` on one device, 1 <= d <= 512,
-1 <= k <= 4096, n >= 0.  Anything else raises; on a GPU there is no torch
-fallback.  CPU tensors run the executable specification below (float64
+Supported: contiguous fp32 or bf16 ``X`` and fp32 ``C`` on one device,
+1 <= d <= 512, 1 <= k <= 4096, n >= 0; ``terms`` in {1, 2, 3} with a bf16
+``X``, 3 with an fp32 ``X`` (which runs exactly as it always has).  Anything
+else raises; on a GPU there is no torch fallback.  CPU tensors run the executable specification below (float64
 distances, first minimum, ``index_add_``).
 
 Numeric contract (u = 2^-24, gamma_m = m u / (1 - m u)):
@@ -28,6 +31,28 @@ Numeric contract (u = 2^-24, gamma_m = m u / (1 - m u)):
 * cost: ``sum_i max(0, |x_i|^2 + score_i)``; within
   ``sum_i (E_i + gamma_{d+2} |x_i|^2) + gamma_n cost`` of the float64 cost.
 * non-finite coordinates: unspecified (labels stay inside [0, k)).
+
+bf16 ``X`` (u~ = 2^-23, gamma~_m = m u~ / (1 - m u~)).  ``split_centroids``
+writes c = c(1) + c(2) + c(3) + rest, piece t the bf16 round-to-nearest-even of
+the residual the pieces before it leave (the residual is exact in fp32), and
+the path minimises the fp32 score against **C_T** = the sum of the first
+``terms`` pieces, which is exactly representable in fp32:
+
+* labels: the chosen centroid is within
+  ``E_i(T) = 2 gamma~_{T d + 2} (|x_i| + max_j |C_T[j]|)^2`` of the float64
+  minimum squared distance to C_T, and IS the float64 argmin over C_T wherever
+  the float64 margin exceeds ``E_i(T)``.  Ties go to the lowest index.
+* the model behind u~: every bf16 x bf16 product is exact in fp32, and the
+  matrix unit's accumulation of m exact terms, in any internal order and with
+  truncation allowed, errs by at most gamma~_m sum |terms|; ``|C_T[j]|^2`` is
+  one length-d fp32 fma chain and the score one more fma.  This is a model of
+  the hardware: it is derived, not measured.
+* T = 3: C_T = C exactly whenever no piece is a bf16 subnormal; centroid
+  coordinates with 0 < |c| < 2^-100 are unspecified.  T = 2 and T = 1 keep 16
+  and 8 significant bits of every centroid coordinate: the answer is the
+  clustering against C_T, which ``split_centroids`` returns.
+* counts, sums and cost keep the bounds above with ``E_i(T)`` for ``E_i``
+  (cost against the float64 cost over C_T).
 """
 from __future__ import annotations
 
@@ -37,12 +62,12 @@ MAX_D = 512
 MAX_K = 4096
 
 
-def _check(X: torch.Tensor, C: torch.Tensor) -> tuple[int, int, int]:
+def _check(X: torch.Tensor, C: torch.Tensor, terms: int = 3) -> tuple[int, int, int]:
     for name, t in (("X", X), ("C", C)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"kmeans: {name} must be a torch tensor (got {type(t).__name__})")
-        if t.dtype != torch.float32:
-            raise TypeError(f"kmeans: {name} must be float32 (got {t.dtype})")
+        if t.dtype != torch.float32 and (name == "C" or t.dtype != torch.bfloat16):
+            raise TypeError(f"kmeans: {name} must be float32{' or bfloat16' if name == 'X' else ''} (got {t.dtype})")
         if t.dim() != 2:
             raise ValueError(f"kmeans: {name} must be 2-D [rows, d] (got {tuple(t.shape)})")
         if not t.is_contiguous():
@@ -57,6 +82,10 @@ def _check(X: torch.Tensor, C: torch.Tensor) -> tuple[int, int, int]:
         raise ValueError(f"kmeans: d = {d} is outside 1..{MAX_D}")
     if not 1 <= k <= MAX_K:
         raise ValueError(f"kmeans: k = {k} is outside 1..{MAX_K}")
+    if terms not in (1, 2, 3):
+        raise ValueError(f"kmeans: terms = {terms!r} is not 1, 2 or 3")
+    if X.dtype == torch.float32 and terms != 3:
+        raise ValueError("kmeans: terms applies to bfloat16 points; float32 points take terms = 3")
     return n, d, k
 
 
@@ -68,21 +97,80 @@ def _acc(t, shape, dtype, device, name):
     return t
 
 
-def lds_limit(d: int) -> int:
-    """Largest k at which a GPU step at this d combines its sums in LDS; a
-    larger k adds straight to the global accumulators."""
+def lds_limit(d: int, dtype: torch.dtype = torch.float32) -> int:
+    """Largest k at which a GPU step at this d, on points of this dtype,
+    combines its sums in LDS; a larger k adds straight to the global
+    accumulators."""
     from . import _hip as H
-    r = int(H.lib().mr_kmeans_lds_limit(int(d)))
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"kmeans: points are float32 or bfloat16 (got {dtype})")
+    name = "mr_kmeans_lds_limit" if dtype == torch.float32 else "mr_kmeans_bf16_lds_limit"
+    r = int(getattr(H.lib(), name)(int(d)))
     if r < 0:
-        raise RuntimeError(f"mr_kmeans_lds_limit({d}) failed: {r}")
+        raise RuntimeError(f"{name}({d}) failed: {r}")
     return r
 
 
-def _launch(X, C, n, d, k, sums, counts, cost, labels) -> None:
+def _workspace(C, d, k, terms):
+    """The bf16 step's workspace (csrc/hip/kmeans_bf16.hip): bf16 planes
+    [terms, kpad, wd], then fp32 cn [kpad].  A torch allocation, so a step is
+    capture-safe under ``torch.cuda.graph``."""
     from . import _hip as H
-    with torch.cuda.device(X.device):
+    kpad, wd = -(-k // 64) * 64, -(-d // 32) * 32
+    nbytes = int(H.lib().mr_kmeans_bf16_workspace_bytes(d, k, terms))
+    if nbytes != 2 * terms * kpad * wd + 4 * kpad:
+        raise RuntimeError(f"mr_kmeans_bf16_workspace_bytes({d}, {k}, {terms}) = {nbytes}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=C.device)
+    planes = ws[:nbytes - 4 * kpad].view(torch.bfloat16).view(terms, kpad, wd)
+    return ws, planes[:, :k, :d], ws[nbytes - 4 * kpad:].view(torch.float32)[:k]
+
+
+def _launch(X, C, n, d, k, sums, counts, cost, labels, terms=3) -> None:
+    from . import _hip as H
+    with torch.cuda.device(C.device):
+        if X is None or X.dtype == torch.bfloat16:
+            ws, planes, cn = _workspace(C, d, k, terms)
+            H.call("mr_kmeans_bf16_step", H.ptr(X), H.ptr(C), n, d, k, terms, H.ptr(ws), H.ptr(sums),
+                   H.ptr(counts), H.ptr(cost), H.ptr(labels), H.stream(C.device))
+            return planes, cn
         H.call("mr_kmeans_step", H.ptr(X), H.ptr(C), n, d, k, H.ptr(sums), H.ptr(counts), H.ptr(cost),
                H.ptr(labels), H.stream(X.device))
+
+
+def _fma32(s, v):
+    """fl32(s + v * v) in one rounding, on fp32 tensors whose v has at most 24
+    significant bits: the product is exact in float64, the float64 sum is
+    rounded to odd (TwoSum gives the sign of what it lost), and 53 >= 24 + 2
+    bits make the second rounding, to fp32, the correct one."""
+    s64, p = s.double(), v.double() * v.double()
+    t = s64 + p
+    b = t - s64
+    err = (s64 - (t - b)) + (p - b)
+    inf = torch.full_like(t, float("inf"))
+    odd = (t.view(torch.int64) & 1).bool()
+    t = torch.where((err != 0) & ~odd, torch.nextafter(t, torch.where(err > 0, inf, -inf)), t)
+    return t.float()
+
+
+def split_centroids(C: torch.Tensor, terms: int = 3):
+    """``(pieces bf16 [terms, k, d], cn fp32 [k])``: piece t is the bf16
+    round-to-nearest-even of ``C`` minus the pieces before it, and ``cn[j]`` is
+    ``|C_T[j]|^2``, C_T the sum of the pieces, as one length-d fp32 fma chain
+    in column order.  On a GPU this is the prologue kernel of a bf16 step; on
+    CPU tensors it is the specification of that kernel, bit for bit."""
+    _n, d, k = _check(C[:0].to(torch.bfloat16), C, terms)
+    if C.is_cuda:
+        planes, cn = _launch(None, C, 0, d, k, None, None, None, None, terms)
+        return planes.contiguous(), cn.contiguous()
+    pieces, rest, ct = [], C.clone(), torch.zeros_like(C)
+    for _ in range(terms):
+        pieces.append(rest.to(torch.bfloat16))  # round to nearest even
+        rest = rest - pieces[-1].float()        # exact
+        ct = ct + pieces[-1].float()            # exact
+    cn = torch.zeros(k, dtype=torch.float32)
+    for c in range(d):
+        cn = _fma32(cn, ct[:, c])
+    return torch.stack(pieces), cn
 
 
 def _spec_labels(X, C):
@@ -98,30 +186,36 @@ def _spec_labels(X, C):
     return lab, best
 
 
-def step(X: torch.Tensor, C: torch.Tensor, sums=None, counts=None, cost=None, labels: bool = False):
+def _spec_centroids(X, C, terms):
+    """The centroids the CPU specification measures against: C, or C_T for bf16 points."""
+    return C if X.dtype == torch.float32 else split_centroids(C, terms)[0].float().sum(0)
+
+
+def step(X: torch.Tensor, C: torch.Tensor, sums=None, counts=None, cost=None, labels: bool = False, terms: int = 3):
     """One assign-and-accumulate step; returns ``(sums, counts, cost, labels | None)``.
-    Accumulators that are given are added into."""
-    n, d, k = _check(X, C)
+    Accumulators that are given are added into.  ``terms``: the bf16 pieces of
+    every centroid a bf16 ``X`` is measured against (see the contract above)."""
+    n, d, k = _check(X, C, terms)
     dev = X.device
     sums = _acc(sums, (k, d), torch.float64, dev, "sums")
     counts = _acc(counts, (k,), torch.int64, dev, "counts")
     cost = _acc(cost, (1,), torch.float64, dev, "cost")
     if X.is_cuda:
         lab = torch.empty(n, dtype=torch.int32, device=dev) if labels else None
-        _launch(X, C, n, d, k, sums, counts, cost, lab)
+        _launch(X, C, n, d, k, sums, counts, cost, lab, terms)
         return sums, counts, cost, lab
-    lab, best = _spec_labels(X, C)
+    lab, best = _spec_labels(X, _spec_centroids(X, C, terms))
     sums.index_add_(0, lab, X.double())
     counts.index_add_(0, lab, torch.ones(n, dtype=torch.int64))
     cost += best.sum()
     return sums, counts, cost, (lab.to(torch.int32) if labels else None)
 
 
-def assign(X: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
+def assign(X: torch.Tensor, C: torch.Tensor, terms: int = 3) -> torch.Tensor:
     """int32 label of every row of X: its nearest centroid (lowest index on ties)."""
-    n, d, k = _check(X, C)
+    n, d, k = _check(X, C, terms)
     if X.is_cuda:
         lab = torch.empty(n, dtype=torch.int32, device=X.device)
-        _launch(X, C, n, d, k, None, None, None, lab)
+        _launch(X, C, n, d, k, None, None, None, lab, terms)
         return lab
-    return _spec_labels(X, C)[0].to(torch.int32)
+    return _spec_labels(X, _spec_centroids(X, C, terms))[0].to(torch.int32)

@@ -8,7 +8,15 @@ answer exits non-zero.  Times are medians of device-event timings after
 warm-up; each shape also gets its two floors, 2 n k d FLOP at the fp32 MFMA
 peak and 4 n d bytes at the HBM peak (datasheet: 157.3 TFLOP/s, 8 TB/s).
 
+``--dtype bf16 [--terms T]`` measures the bf16 step (csrc/hip/kmeans_bf16.hip)
+instead, by the same method.  Its partner is the fp32 ``ops.kmeans.step`` on the
+same points widened to fp32 (the kernel the line above measures), and the
+sample is validated against the CPU specification of the bf16 path (C_T,
+u~ = 2^-23, E_i(T)).  Floors: 2 T n k d FLOP at the bf16 matrix peak
+(datasheet: 2.5 PFLOP/s dense) and 2 n d bytes at the HBM peak.
+
     python tools/bench_kmeans.py [--n 16777216] [--steps 5] [--warmup 2] [--shapes 16x16,64x256]
+                                 [--dtype bf16 [--terms 3]]
 """
 import argparse
 import json
@@ -23,6 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lua_mapreduce_1_amd.ops import kmeans as K  # noqa: E402
 
 PEAK_FLOPS = 157.3e12  # MI355X fp32 matrix
+PEAK_BF16 = 2.5e15     # MI355X bf16 matrix, dense (datasheet, not measured here)
 PEAK_BYTES = 8.0e12    # MI355X HBM3E
 U = 2.0 ** -24
 
@@ -50,16 +59,18 @@ def torch_chain(X, C):
     return sums, counts
 
 
-def validate(X, C, rows=4096):
-    """One kernel step on a strided sample against the CPU specification."""
+def validate(X, C, rows=4096, terms=3):
+    """One kernel step on a strided sample against the CPU specification
+    (bf16 points: against C_T, with the bf16 path's E_i(T))."""
     n, d = X.shape
     xs = X[::max(1, n // rows)][:rows].contiguous()
-    sums, counts, cost, lab = K.step(xs, C, labels=True)
-    s64, c64, q64, l64 = K.step(xs.cpu(), C.cpu(), labels=True)
-    X64, C64 = xs.cpu().double(), C.cpu().double()
+    sums, counts, cost, lab = K.step(xs, C, labels=True, terms=terms)
+    s64, c64, q64, l64 = K.step(xs.cpu(), C.cpu(), labels=True, terms=terms)
+    X64, C64 = xs.cpu().double(), K._spec_centroids(xs, C.cpu(), terms).double()
     D = torch.cdist(X64, C64) ** 2
     g = (d + 2) * U / (1 - (d + 2) * U)
-    E = 2 * g * (X64.norm(dim=1) + C64.norm(dim=1).max()) ** 2
+    gl = g if X.dtype == torch.float32 else 2 * (terms * d + 2) * U / (1 - 2 * (terms * d + 2) * U)
+    E = 2 * gl * (X64.norm(dim=1) + C64.norm(dim=1).max()) ** 2
     lab = lab.cpu().long()
     best = D.min(1).values
     ok = bool((D.gather(1, lab[:, None])[:, 0] <= best + E + 1e-9 * best).all())  # (1e-9: cdist's own rounding)
@@ -89,13 +100,45 @@ def timed(fn, steps, warmup):
     return out
 
 
+def bench_bf16(a, X, X32, C, box):
+    """The bf16 step on X against the fp32 step on the same points widened to fp32; 1 if invalid."""
+    n, (k, d) = a.n, C.shape
+    X32.copy_(X)
+    valid = validate(X, C, terms=a.terms)
+
+    def acc():
+        return (torch.zeros(k, d, dtype=torch.float64, device=X.device),
+                torch.zeros(k, dtype=torch.int64, device=X.device), torch.zeros(1, dtype=torch.float64, device=X.device))
+    ab, af = acc(), acc()
+    tb, tf = [], []
+    for _ in range(a.steps):  # alternate the two, one timed call each per round
+        tb += timed(lambda: K.step(X, C, *ab, terms=a.terms), 1, a.warmup if not tb else 0)
+        tf += timed(lambda: K.step(X32, C, *af), 1, a.warmup if not tf else 0)
+    calls = a.steps + a.warmup
+    valid &= int(ab[1].sum()) == calls * n
+    # C_T and C may split near-ties differently: counts agree to within a 1e-3 share at T = 3
+    valid &= a.terms < 3 or float((ab[1] - af[1]).abs().sum()) <= 1e-3 * n * calls
+    ms_b, ms_f = statistics.median(tb), statistics.median(tf)
+    f_flop, f_byte = 2.0 * a.terms * n * k * d / PEAK_BF16 * 1e3, 2.0 * n * d / PEAK_BYTES * 1e3
+    print(json.dumps({"box": box, "dtype": "bf16", "terms": a.terms, "n": n, "d": d, "k": k, "valid": bool(valid),
+                      "bf16_ms": round(ms_b, 3), "bf16_ms_all": [round(t, 3) for t in tb], "fp32_ms": round(ms_f, 3),
+                      "fp32_ms_all": [round(t, 3) for t in tf], "fp32_over_bf16": round(ms_f / ms_b, 2),
+                      "mfma_floor_ms": round(f_flop, 4), "hbm_floor_ms": round(f_byte, 3),
+                      "mfma_fraction": round(f_flop / ms_b, 3), "hbm_fraction": round(f_byte / ms_b, 3)}), flush=True)
+    return 0 if valid else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 24)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--shapes", default=",".join(f"{d}x{k}" for d in (16, 64, 128) for k in (16, 256, 1024)))
+    ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32")
+    ap.add_argument("--terms", type=int, default=3)
     a = ap.parse_args()
+    if a.dtype == "fp32" and a.terms != 3:
+        ap.error("--terms goes with --dtype bf16")
     if not torch.cuda.is_available():
         sys.exit("bench_kmeans needs a GPU: nothing is measured without one")
     dev = torch.device("cuda", 0)
@@ -104,6 +147,10 @@ def main():
     for shape in a.shapes.split(","):
         d, k = (int(v) for v in shape.split("x"))
         X, C = make(a.n, d, k, dev)
+        if a.dtype == "bf16":
+            bad += bench_bf16(a, X.to(torch.bfloat16), X, C, box)
+            del X, C
+            continue
         valid = validate(X, C)
         sums = torch.zeros(k, d, dtype=torch.float64, device=dev)
         counts = torch.zeros(k, dtype=torch.int64, device=dev)

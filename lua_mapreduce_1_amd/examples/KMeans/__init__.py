@@ -31,8 +31,30 @@ scope here.
   centroid; ``HISTORY`` gets ``{iter, cost, shift, empty}``; ``"loop"`` until
   the shift is <= tol or ``max_iters`` is reached.  Afterwards ``CENTROIDS``
   (device tensor) and ``predict(X)`` (``ops.kmeans.assign``) serve the model.
+* ``init_method``: ``"rows"`` (default: the k random rows above) or
+  ``"kmeans||"`` (Bahmani et al., "Scalable K-Means++"), with ``seed_ell``
+  (2k: the expected picks of a round) and ``seed_rounds`` (5).  The first
+  engine iterations are then seeding rounds, a phase of the module state: the
+  map runs ``ops.kmeans.min_dist`` (csrc/hip/kmeans_seed.hip) on the job's
+  resident points against the replicated newest batch of candidates, keeps
+  ``mind`` / ``near`` per job beside the points and adds ``phi`` into ``COST``;
+  the final, on every rank, runs ``ops.kmeans.sample`` over its own jobs with
+  the job's global row offset (the selection does not depend on how the points
+  are split), exchanges the picks with ``all_gather_object``, orders them by
+  global index and appends them to the candidates.  One more iteration folds
+  the last batch, the per-job ``bincount(near)`` are summed across ranks, and
+  every rank sets ``CENTROIDS = ops.kmeans.recluster(...)`` with the same seed.
+  Lloyd's then proceeds as above: ``HISTORY`` and ``max_iters`` count Lloyd
+  iterations only; the seeding rounds go to ``SEED_HISTORY`` (``{round, phi,
+  candidates}``) and ``SEED_INFO`` (``indices`` per round, ``candidates``,
+  ``weights``, ``seeds``).  Seeding rounds are not checkpointed.
 * ``naive(splits, ...)``: plain float64 numpy Lloyd's with the same init, tie
-  rule, empty-cluster rule and stopping rule.
+  rule, empty-cluster rule and stopping rule; with ``init_method="kmeans||"``
+  the same seeding in float64 with the same hash and rule, and the result also
+  holds ``seed_indices`` (per round) and ``seed_margin``: for every point the
+  smallest relative distance ``|u phi - ell' mind| / (ell' mind)`` of the rule's
+  two sides over the rounds (ell' = ell 2^24), i.e. how far the selection is
+  from depending on rounding.
 """
 from __future__ import annotations
 
@@ -41,6 +63,7 @@ import torch
 
 from lua_mapreduce_1_amd.ops import io as _io
 from lua_mapreduce_1_amd.ops import kmeans as K
+from lua_mapreduce_1_amd.parallel import dist as D
 
 NUM_REDUCERS = 10
 KEYS = ("SUMS", "COUNTS", "COST")
@@ -50,6 +73,8 @@ device_reduce = "tensor_sum"
 spmd_replicated_taskfn = True
 
 HISTORY: list = []
+SEED_HISTORY: list = []
+SEED_INFO: dict = {}
 CENTROIDS = None
 _st: dict = {}
 
@@ -85,17 +110,22 @@ def _values(rows: np.ndarray) -> np.ndarray:
     return widen(rows) if rows.dtype == np.uint16 else rows
 
 
-def initial_centroids(splits, k: int, dim: int, seed: int, point_dtype: str = "fp32") -> np.ndarray:
-    """k distinct rows of the concatenated splits, the same on every rank."""
+def take_rows(splits, pick, dim: int, point_dtype: str = "fp32") -> np.ndarray:
+    """Rows ``pick`` (global indices) of the concatenated splits, fp32."""
     splits = [_rows(s, dim, point_dtype) for s in splits]
     sizes = [s.shape[0] for s in splits]
-    pick = np.random.default_rng(seed).choice(int(sum(sizes)), k, replace=False)
     ends = np.cumsum(sizes)
-    out = np.empty((k, dim), dtype=np.float32)
+    out = np.empty((len(pick), dim), dtype=np.float32)
     for j, r in enumerate(pick):
         s = int(np.searchsorted(ends, r, side="right"))
         out[j] = _values(splits[s][r - (ends[s] - sizes[s])])
     return out
+
+
+def initial_centroids(splits, k: int, dim: int, seed: int, point_dtype: str = "fp32") -> np.ndarray:
+    """k distinct rows of the concatenated splits, the same on every rank."""
+    total = sum(_rows(s, dim, point_dtype).shape[0] for s in splits)
+    return take_rows(splits, np.random.default_rng(seed).choice(int(total), k, replace=False), dim, point_dtype)
 
 
 def split_counts(c: torch.Tensor) -> torch.Tensor:
@@ -111,10 +141,10 @@ def rejoin_counts(t: torch.Tensor) -> torch.Tensor:
 
 
 def init(args):
-    global HISTORY, CENTROIDS
+    global HISTORY, SEED_HISTORY, SEED_INFO, CENTROIDS
     a = dict(args or {})
     _st.clear()
-    HISTORY = []
+    HISTORY, SEED_HISTORY, SEED_INFO = [], [], {}
     CENTROIDS = None
     k, dim = int(a["k"]), int(a["dim"])
     files = a.get("files", "synthetic")
@@ -129,14 +159,28 @@ def init(args):
     else:
         splits = [files] if isinstance(files, str) else list(files)
     c = a.get("centroids")
-    if c is None:
+    method = a.get("init_method", "rows")
+    if method not in ("rows", "kmeans||"):
+        raise ValueError(f"KMeans: init_method is 'rows' or 'kmeans||' (got {method!r})")
+    seeding = None
+    if method == "kmeans||":
+        if c is not None:
+            raise ValueError("KMeans: init_method 'kmeans||' and centroids exclude each other")
+        sizes = [_rows(s, dim, dt).shape[0] for s in splits]
+        first = np.array([np.random.default_rng(seed).integers(int(sum(sizes)))], dtype=np.int64)
+        seeding = dict(ell=float(a.get("seed_ell", 2 * k)), rounds=int(a.get("seed_rounds", 5)), total=0, jobs={},
+                       offsets=[int(o) for o in np.cumsum([0] + sizes[:-1])], indices=[first],
+                       batches=[take_rows(splits, first, dim, dt)])
+        c0 = np.zeros((k, dim), dtype=np.float32)  # never read: the seeding sets CENTROIDS
+    elif c is None:
         c0 = initial_centroids(splits, k, dim, seed, dt)
     elif isinstance(c, str):
         c0 = np.fromfile(c, dtype="<f4").reshape(k, dim)
     else:
         c0 = np.asarray(c, dtype=np.float32).reshape(k, dim)
     _st.update(k=k, dim=dim, splits=splits, c0=np.ascontiguousarray(c0, dtype=np.float32), points={},
-               max_iters=int(a.get("max_iters", 20)), tol=float(a.get("tol", 1e-4)), bf16=dt == "bf16", terms=terms)
+               max_iters=int(a.get("max_iters", 20)), tol=float(a.get("tol", 1e-4)), bf16=dt == "bf16", terms=terms,
+               seed=seed, seeding=seeding)
 
 
 def taskfn(emit):
@@ -181,11 +225,61 @@ def device_mapfn(key, value, emit):
     """Assign the job's points (device-resident after the first iteration) to
     the replicated centroids and add the partial sums into the plane."""
     dev = emit.device
+    if _st["seeding"] is not None:
+        return _seed_map(key, _points(key, value, dev), emit)
     sums, counts, cost, _ = K.step(_points(key, value, dev), _centroids(dev), terms=_st["terms"])
     emit.accumulator("SUMS").add_(sums.reshape(-1).to(torch.float32))
     cw = emit.accumulator("COUNTS")
     cw.copy_(split_counts(rejoin_counts(cw) + counts))  # add, then renormalise the two words
     emit.accumulator("COST").add_(cost.to(torch.float32))
+
+
+def _seed_map(key, x, emit):
+    """A seeding round's map: fold the newest batch of candidates into the job's mind / near."""
+    sd = _st["seeding"]
+    batch = torch.from_numpy(sd["batches"][-1]).to(x.device)
+    mind, near = sd["jobs"].get(key, (None, None))
+    for i in range(0, len(batch), K.MAX_M):  # a batch beyond the kernel's range goes in pieces
+        mind, near, phi = K.min_dist(x, batch[i:i + K.MAX_M].contiguous(), mind, near, base=sd["total"] + i)
+    sd["jobs"][key] = (mind, near)
+    emit.accumulator("COST").add_(phi.to(torch.float32))
+
+
+def _seed_final(res, engine):
+    """A seeding round's final, on every rank: sample the next batch, or, after
+    the last fold, weigh the candidates and pick the k seeds."""
+    global CENTROIDS
+    sd = _st["seeding"]
+    phi = float(res.tensors["COST"][0])
+    sd["total"] += len(sd["batches"][-1])
+    t = len(SEED_HISTORY)
+    picked = 0
+    if t < sd["rounds"]:
+        mine = []
+        for key, (mind, _near) in sd["jobs"].items():
+            idx, rows = K.sample(_st["points"][key], mind, phi, sd["ell"], _st["seed"], t,
+                                 offset=sd["offsets"][int(key) - 1])
+            mine.append((idx.cpu().numpy(), rows.cpu().numpy()))
+        got = [p for r in D.all_gather_object(mine, engine.group) for p in r]
+        idx = np.concatenate([p[0] for p in got]) if got else np.zeros(0, dtype=np.int64)
+        order = np.argsort(idx, kind="stable")
+        picked = len(idx)
+        if picked:
+            sd["indices"].append(idx[order])
+            sd["batches"].append(np.concatenate([p[1] for p in got])[order])
+    SEED_HISTORY.append({"round": t + 1, "phi": phi, "candidates": sd["total"] + picked})
+    if engine.rank == 0 and engine.verbose:
+        print("# kmeans|| round %(round)d phi %(phi).6g candidates %(candidates)d" % SEED_HISTORY[-1], flush=True)
+    if picked:
+        return "loop"  # the next iteration folds the new batch
+    mine = sum(torch.bincount(near.long(), minlength=sd["total"]).cpu().numpy() for _m, near in sd["jobs"].values())
+    weights = sum(D.all_gather_object(mine, engine.group))
+    cands = np.concatenate(sd["batches"])
+    CENTROIDS = K.recluster(cands, weights, _st["k"], _st["seed"]).to(engine.device)
+    SEED_INFO.update(indices=sd["indices"], candidates=cands, weights=np.asarray(weights),
+                     seeds=CENTROIDS.cpu().numpy())
+    _st["seeding"] = None
+    return "loop"
 
 
 def partitionfn(key):
@@ -199,6 +293,8 @@ def reducefn(key, values, emit):
 def device_finalfn(res, engine):
     """Every rank: move the centroids, record the iteration, decide to loop."""
     global CENTROIDS
+    if _st["seeding"] is not None:
+        return _seed_final(res, engine)
     k, dim = _st["k"], _st["dim"]
     old = _centroids(engine.device)
     counts = rejoin_counts(res.tensors["COUNTS"])
@@ -228,11 +324,44 @@ def predict(X) -> torch.Tensor:
     return K.assign(x.to(CENTROIDS.device).contiguous(), CENTROIDS, terms=_st["terms"])
 
 
+def _naive_seed(X: np.ndarray, k: int, ell: float, rounds: int, seed: int) -> dict:
+    """k-means|| in float64 numpy, round for round as the job runs it."""
+    n = len(X)
+    g = np.arange(n, dtype=np.uint64)
+    indices = [np.array([np.random.default_rng(seed).integers(n)], dtype=np.int64)]
+    mind, near, total, margin = np.full(n, np.inf), np.full(n, -1, dtype=np.int64), 0, np.full(n, np.inf)
+    for t in range(rounds + 1):
+        B = X[indices[-1]]
+        for i in range(0, n, 8192):
+            Dm = ((X[i:i + 8192, None, :] - B[None]) ** 2).sum(-1)
+            j = Dm.argmin(1)
+            take = Dm[np.arange(len(j)), j] < mind[i:i + 8192]
+            mind[i:i + 8192][take] = Dm[np.arange(len(j)), j][take]
+            near[i:i + 8192][take] = total + j[take]
+        total += len(B)
+        phi = float(mind.sum())
+        if t == rounds:
+            break
+        lhs, rhs = K._u24(seed, t, g).astype(np.float64) * phi, ell * 2.0 ** 24 * mind
+        margin = np.minimum(margin, np.where(rhs > 0, np.abs(lhs - rhs) / np.where(rhs > 0, rhs, 1.0), np.inf))
+        pick = np.flatnonzero(K.selected(mind, phi, ell, seed, t, g))
+        if len(pick) == 0:
+            break
+        indices.append(pick)
+    weights = np.bincount(near, minlength=total)
+    C = K.recluster(X[np.concatenate(indices)].astype(np.float32), weights, k, seed).numpy()
+    return {"centroids": C, "seed_indices": indices, "seed_margin": margin, "seed_weights": weights}
+
+
 def naive(splits, k: int, dim: int, max_iters: int = 20, tol: float = 1e-4, seed: int = 0, centroids=None,
-          point_dtype: str = "fp32") -> dict:
+          point_dtype: str = "fp32", init_method: str = "rows", seed_ell=None, seed_rounds: int = 5) -> dict:
     """Plain float64 numpy Lloyd's: the oracle of the job above (bf16 points:
     uint16 rows or bf16 files, i.e. the rounded points the job itself sees)."""
     X = np.concatenate([_values(np.asarray(_rows(s, dim, point_dtype))) for s in splits]).astype(np.float64)
+    extra = {}
+    if init_method == "kmeans||" and centroids is None:
+        extra = _naive_seed(X, k, float(2 * k if seed_ell is None else seed_ell), seed_rounds, seed)
+        centroids = extra.pop("centroids")
     C = (initial_centroids(splits, k, dim, seed, point_dtype) if centroids is None
          else np.asarray(centroids, dtype=np.float32).reshape(k, dim)).astype(np.float64)
     history = []
@@ -251,4 +380,4 @@ def naive(splits, k: int, dim: int, max_iters: int = 20, tol: float = 1e-4, seed
         C = new
         history.append({"iter": len(history) + 1, "cost": cost, "shift": shift, "empty": int((counts == 0).sum())})
         if not (shift > tol and len(history) < max_iters):
-            return {"centroids": C, "history": history}
+            return {"centroids": C, "history": history, **extra}

@@ -68,6 +68,12 @@ _SIGS = {
     "mr_kmeans_bf16_step": [_p, _p, ctypes.c_longlong, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p],
     "mr_kmeans_bf16_workspace_bytes": [_i32, _i32, _i32],
     "mr_kmeans_bf16_lds_limit": [_i32],
+    "mr_kmeans_seed_partials": [],
+    "mr_kmeans_min_dist": [_p, _i32, _p, ctypes.c_longlong, _i32, _i32, _p, _p, _i32, _p, _p, _p],
+    "mr_kmeans_sample_count": [_p, ctypes.c_longlong, _u64, ctypes.c_double, ctypes.c_double, _u32, _u32, _p, _p, _p,
+                               _p],
+    "mr_kmeans_sample_write": [_p, _i32, _p, ctypes.c_longlong, _i32, _u64, ctypes.c_double, ctypes.c_double, _u32,
+                               _u32, _p, _p, _p, _p],
     "mr_count_newlines": [_p, _u64, _u64, _p, _p, _p],
     "mr_ii_map": [_p, _u64, _u64, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _u64, _u32, _p, _p, _u64, _p, _p],
     "mr_ii_advance": [_p, _p, _p],

@@ -53,16 +53,50 @@ the path minimises the fp32 score against **C_T** = the sum of the first
   clustering against C_T, which ``split_centroids`` returns.
 * counts, sums and cost keep the bounds above with ``E_i(T)`` for ``E_i``
   (cost against the float64 cost over C_T).
+
+Seeding (k-means||, Bahmani et al., "Scalable K-Means++";
+csrc/hip/kmeans_seed.hip).  ``min_dist(X, C, mind, near, base)`` folds the new
+candidates ``C`` [m, d], 1 <= m <= 16384, into every point's running nearest-
+candidate squared distance ``mind`` (fp32) and index ``near`` (int32, ``base +
+j``; an earlier candidate keeps a tie) and returns ``phi``, the float64 sum of
+``mind`` after the fold.  ``sample`` draws the next batch from it, ``recluster``
+reduces the weighted candidates to k seeds on the host, ``seed`` drives the
+rounds on one device.  bf16 points are widened exactly to fp32 and run the fp32
+matrix path; a bf16-MFMA seeding path is out of scope.  With ``E_i`` as above
+(``max_j`` over this call's ``C``), ``D_i`` the float64 minimum squared
+distance to ``C`` and ``B_i = E_i + gamma_{d+2} |x_i|^2 + 2 u (D_i + E_i)``
+(the score, ``fl(|x|^2)``, and the final add and clamp):
+
+* after one call from fresh state ``|mind_i - D_i| <= B_i``;
+* over several calls ``D64[i, near_i]`` is within ``2 B_i`` of the float64
+  minimum over all candidates seen (``B_i`` with ``max_j`` over all of them),
+  and ``near_i`` IS that argmin wherever the float64 margin exceeds ``2 B_i``;
+* ``phi`` equals the float64 sum of the returned ``mind`` to within
+  ``gamma'_n sum mind`` (u' = 2^-53), and is bitwise reproducible for equal
+  inputs on one device (fixed slots, fixed order, no float atomics);
+* ``sample`` is exact.  Point ``i``, global index ``g = offset + i``, is
+  selected iff ``phi != 0`` and ``float64(u24) * phi < (ell 2^24) *
+  float64(mind_i)``, one IEEE multiply a side, where ``u24`` is the top 24 bits
+  of ``F(F(F(F(seed + 0x9E3779B9) ^ round) ^ hi32(g)) ^ lo32(g))`` in 32-bit
+  arithmetic and ``F`` is murmur3's finaliser (``h ^= h >> 16; h *= 0x85EBCA6B;
+  h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16``).  ``F`` is a bijection, so
+  over 2^32 consecutive ``g`` every ``u24`` occurs equally often.  Given the
+  same ``mind``, ``phi`` and integers, the GPU and the CPU path (``_u24``
+  below: the specification, bit for bit) return identical ``idx`` (ascending
+  global indices) and ``rows`` (fp32, ``X[idx - offset]`` widened).
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 MAX_D = 512
 MAX_K = 4096
+MAX_M = 16384
 
 
-def _check(X: torch.Tensor, C: torch.Tensor, terms: int = 3) -> tuple[int, int, int]:
+def _check(X: torch.Tensor, C: torch.Tensor, terms: int = 3, limit: int = MAX_K,
+           rows: str = "k") -> tuple[int, int, int]:
     for name, t in (("X", X), ("C", C)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"kmeans: {name} must be a torch tensor (got {type(t).__name__})")
@@ -80,8 +114,8 @@ def _check(X: torch.Tensor, C: torch.Tensor, terms: int = 3) -> tuple[int, int, 
         raise ValueError(f"kmeans: X has d = {d}, C has d = {C.shape[1]}")
     if not 1 <= d <= MAX_D:
         raise ValueError(f"kmeans: d = {d} is outside 1..{MAX_D}")
-    if not 1 <= k <= MAX_K:
-        raise ValueError(f"kmeans: k = {k} is outside 1..{MAX_K}")
+    if not 1 <= k <= limit:
+        raise ValueError(f"kmeans: {rows} = {k} is outside 1..{limit}")
     if terms not in (1, 2, 3):
         raise ValueError(f"kmeans: terms = {terms!r} is not 1, 2 or 3")
     if X.dtype == torch.float32 and terms != 3:
@@ -219,3 +253,163 @@ def assign(X: torch.Tensor, C: torch.Tensor, terms: int = 3) -> torch.Tensor:
         _launch(X, C, n, d, k, None, None, None, lab, terms)
         return lab
     return _spec_labels(X, _spec_centroids(X, C, terms))[0].to(torch.int32)
+
+
+# ---- k-means|| seeding (csrc/hip/kmeans_seed.hip; contract in the module docstring) -------------
+
+_M32 = 0xFFFFFFFF
+
+
+def _fmix(h):
+    """murmur3's 32-bit finaliser on a Python int or a uint64 array of 32-bit values."""
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & _M32
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & _M32
+    return h ^ (h >> 16)
+
+
+def _u24(seed: int, round: int, g: np.ndarray) -> np.ndarray:
+    """The sampling hash: top 24 bits of F(F(F(F(seed + 0x9E3779B9) ^ round) ^ hi32(g)) ^ lo32(g))."""
+    g = np.asarray(g, dtype=np.uint64)
+    hs = np.uint64(_fmix(_fmix((int(seed) + 0x9E3779B9) & _M32) ^ (int(round) & _M32)))
+    return _fmix(_fmix(hs ^ (g >> np.uint64(32))) ^ (g & np.uint64(_M32))) >> np.uint64(8)
+
+
+def selected(mind, phi: float, ell: float, seed: int, round: int, g) -> np.ndarray:
+    """The selection rule on host arrays: ``mind`` of the points with global indices ``g``."""
+    with np.errstate(invalid="ignore"):
+        lhs = _u24(seed, round, g).astype(np.float64) * np.float64(phi)
+        return (np.float64(phi) != 0) & (lhs < np.float64(float(ell) * 2.0 ** 24) * np.asarray(mind, dtype=np.float64))
+
+
+def _state(t, n, dtype, fill, device, name):
+    return torch.full((n,), fill, dtype=dtype, device=device) if t is None else _acc(t, (n,), dtype, device, name)
+
+
+def min_dist(X: torch.Tensor, C: torch.Tensor, mind=None, near=None, base: int = 0):
+    """Fold the new candidates ``C`` into ``mind`` / ``near`` (``None``: fresh
+    state, +inf / -1; given tensors are updated in place); returns
+    ``(mind, near, phi)``, ``phi`` float64 [1]."""
+    n, d, m = _check(X, C, limit=MAX_M, rows="m")
+    dev = X.device
+    mind = _state(mind, n, torch.float32, float("inf"), dev, "mind")
+    near = _state(near, n, torch.int32, -1, dev, "near")
+    if not 0 <= int(base) <= 2 ** 31 - 1 - m:
+        raise ValueError(f"kmeans: base = {base!r} with m = {m} leaves int32")
+    phi = torch.empty(1, dtype=torch.float64, device=dev)
+    if X.is_cuda:
+        from . import _hip as H
+        with torch.cuda.device(dev):
+            part = torch.empty(int(H.lib().mr_kmeans_seed_partials()), dtype=torch.float64, device=dev)
+            H.call("mr_kmeans_min_dist", H.ptr(X), int(X.dtype == torch.bfloat16), H.ptr(C), n, d, m, H.ptr(mind),
+                   H.ptr(near), int(base), H.ptr(part), H.ptr(phi), H.stream(dev))
+        return mind, near, phi
+    lab, best = _spec_labels(X, C)
+    dist = best.float()
+    take = dist < mind  # strict: an earlier candidate keeps a tie
+    mind[take] = dist[take]
+    near[take] = (int(base) + lab[take]).to(torch.int32)
+    phi[0] = mind.double().sum()
+    return mind, near, phi
+
+
+def sample(X: torch.Tensor, mind: torch.Tensor, phi, ell: float, seed: int, round: int, offset: int = 0):
+    """Bernoulli D^2 sampling: ``(idx int64 [s], rows fp32 [s, d])``, the
+    selected points' global indices ``offset + i``, ascending, and their rows."""
+    if not isinstance(X, torch.Tensor) or X.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("kmeans: X must be a float32 or bfloat16 torch tensor")
+    if X.dim() != 2 or not X.is_contiguous() or not 1 <= X.shape[1] <= MAX_D:
+        raise ValueError(f"kmeans: X must be contiguous [n, d] with d in 1..{MAX_D} (got {tuple(X.shape)})")
+    n, d = X.shape
+    if not isinstance(mind, torch.Tensor) or mind.dtype != torch.float32:
+        raise TypeError("kmeans: mind must be a float32 torch tensor")
+    _acc(mind, (n,), torch.float32, X.device, "mind")
+    phi, ell, offset = float(phi), float(ell), int(offset)
+    if not ell > 0 or ell == float("inf"):
+        raise ValueError(f"kmeans: ell = {ell!r} is not a positive finite number")
+    if not 0 <= offset <= 2 ** 63 - 1 - n:
+        raise ValueError(f"kmeans: offset = {offset!r} leaves int64")
+    seed, round = int(seed) & _M32, int(round) & _M32
+    if X.is_cuda:
+        from . import _hip as H
+        dev = X.device
+        nb = -(-n // 4096)
+        counts = torch.empty(nb, dtype=torch.int32, device=dev)
+        offs = torch.empty(nb, dtype=torch.int64, device=dev)
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        rule = (offset, phi, ell * 2.0 ** 24, seed, round)
+        with torch.cuda.device(dev):
+            H.call("mr_kmeans_sample_count", H.ptr(mind), n, *rule, H.ptr(counts), H.ptr(offs), H.ptr(total),
+                   H.stream(dev))
+            s = int(total.item())  # the one synchronisation: it sizes the outputs
+            idx = torch.empty(s, dtype=torch.int64, device=dev)
+            rows = torch.empty((s, d), dtype=torch.float32, device=dev)
+            if s:
+                H.call("mr_kmeans_sample_write", H.ptr(X), int(X.dtype == torch.bfloat16), H.ptr(mind), n, d, *rule,
+                       H.ptr(offs), H.ptr(idx), H.ptr(rows), H.stream(dev))
+        return idx, rows
+    g = np.uint64(offset) + np.arange(n, dtype=np.uint64)
+    pick = torch.from_numpy(np.flatnonzero(selected(mind.numpy(), phi, ell, seed, round, g)))
+    return pick + offset, X[pick].float()
+
+
+def recluster(cands, weights, k: int, seed: int) -> torch.Tensor:
+    """Weighted k-means++ over the candidates, in float64 numpy on the host:
+    the first pick is drawn with probability proportional to weight, every
+    later one to weight x D^2 (to the picks so far), from ``default_rng(seed)``.
+    Returns the k picked rows, fp32, on the candidates' device."""
+    dev = cands.device if isinstance(cands, torch.Tensor) else torch.device("cpu")
+    P = (cands.detach().cpu().numpy() if isinstance(cands, torch.Tensor) else np.asarray(cands)).astype(np.float64)
+    w = (weights.detach().cpu().numpy() if isinstance(weights, torch.Tensor) else np.asarray(weights)) \
+        .astype(np.float64)
+    if P.ndim != 2 or w.shape != (len(P),) or (w < 0).any():
+        raise ValueError(f"kmeans: candidates {P.shape} need one weight >= 0 each (got {w.shape})")
+    if int((w > 0).sum()) < int(k) or k < 1:
+        raise ValueError(f"kmeans: k = {k} seeds need as many candidates of positive weight (got {int((w > 0).sum())})")
+    rng = np.random.default_rng(seed)
+    picks = [int(rng.choice(len(P), p=w / w.sum()))]
+    D = ((P - P[picks[0]]) ** 2).sum(1)
+    for _ in range(k - 1):
+        p = w * D
+        if not p.sum() > 0:  # the rest coincide with picks: any unpicked candidate of positive weight
+            p = w.copy()
+            p[picks] = 0
+        picks.append(int(rng.choice(len(P), p=p / p.sum())))
+        D = np.minimum(D, ((P - P[picks[-1]]) ** 2).sum(1))
+        D[picks[-1]] = 0.0
+    return torch.from_numpy(P[picks].astype(np.float32)).to(dev)
+
+
+def seed(X: torch.Tensor, k: int, ell: float | None = None, rounds: int = 5, seed: int = 0):
+    """k-means|| on one device: ``(C0 fp32 [k, d], info)``.  The first candidate
+    is row ``default_rng(seed).integers(n)``; each of ``rounds`` rounds folds the
+    newest batch (``min_dist``, ``base`` = the candidates so far) and samples
+    the next with ``ell`` (default 2k) expected picks; the last batch is folded,
+    every candidate is weighted by the points nearest to it and ``recluster``
+    picks the k seeds.  ``info``: ``candidates``, ``weights``, ``phi`` per round."""
+    if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.shape[0] < 1:
+        raise ValueError("kmeans: seed needs a non-empty [n, d] tensor of points")
+    ell = 2.0 * k if ell is None else float(ell)
+    first = int(np.random.default_rng(seed).integers(X.shape[0]))
+    cands, batch, mind, near, phis = [], X[first:first + 1].float().contiguous(), None, None, []
+
+    def fold(batch, mind, near):
+        phi = None
+        for i in range(0, len(batch), MAX_M):  # a batch beyond the kernel's range goes in pieces
+            mind, near, phi = min_dist(X, batch[i:i + MAX_M].contiguous(), mind, near,
+                                       base=sum(len(c) for c in cands) + i)
+        cands.append(batch)
+        return mind, near, phi
+
+    for r in range(int(rounds)):
+        mind, near, phi = fold(batch, mind, near)
+        phis.append(float(phi))
+        _idx, batch = sample(X, mind, phi, ell, seed, r)
+        if len(batch) == 0:
+            break
+    if len(batch):
+        mind, near, _phi = fold(batch, mind, near)
+    cands = torch.cat(cands)
+    weights = torch.bincount(near.long(), minlength=len(cands)).cpu()
+    return recluster(cands, weights, k, seed), {"candidates": cands, "weights": weights, "phi": phis}

@@ -15,8 +15,17 @@ sample is validated against the CPU specification of the bf16 path (C_T,
 u~ = 2^-23, E_i(T)).  Floors: 2 T n k d FLOP at the bf16 matrix peak
 (datasheet: 2.5 PFLOP/s dense) and 2 n d bytes at the HBM peak.
 
+``--op seed`` measures the k-means|| seeding path (csrc/hip/kmeans_seed.hip) at
+the same shapes with m = 2k candidates (rows of X): one ``min_dist`` round from
+fresh state against the torch chain ``(|x|^2 + |c|^2 - 2 X @ C.T).min(1)``
+folded into ``mind`` in row blocks, and against ``ops.kmeans.assign`` at the
+same (d, m), alternating; ``sample`` alone (its host read of the total
+included); and Lloyd's iteration count and final cost from "rows" against
+"kmeans||" seeds (``ops.kmeans.seed``, timed as a whole).  A sample of the
+``min_dist`` result is validated against float64 with the bound B_i first.
+
     python tools/bench_kmeans.py [--n 16777216] [--steps 5] [--warmup 2] [--shapes 16x16,64x256]
-                                 [--dtype bf16 [--terms 3]]
+                                 [--dtype bf16 [--terms 3]] [--op seed]
 """
 import argparse
 import json
@@ -128,6 +137,88 @@ def bench_bf16(a, X, X32, C, box):
     return 0 if valid else 1
 
 
+def lloyd(X, C, max_iters=20, tol=1e-4):
+    """Lloyd's from C with ops.kmeans.step: (iterations, final cost)."""
+    for it in range(1, max_iters + 1):
+        sums, counts, cost, _ = K.step(X, C)
+        new = torch.where((counts > 0)[:, None], sums / counts.clamp(min=1)[:, None], C.double())
+        shift = float(((new - C.double()) ** 2).sum(1).max())
+        C = new.float().contiguous()
+        if shift <= tol:
+            break
+    return it, float(cost)
+
+
+def bench_seed(a, X, box, d, k):
+    """One min_dist round against the torch chain and against assign, sample alone, Lloyd's from both inits."""
+    n, m, dev = a.n, 2 * k, X.device
+    g = torch.Generator(device=dev).manual_seed(2)
+    Cm = X[torch.randint(0, n, (m,), device=dev, generator=g)].contiguous()
+    xs = X[::max(1, n // 4096)][:4096].contiguous()  # validation: a sample against float64, bound B_i
+    md, _nr, ph = K.min_dist(xs, Cm)
+    X64, C64 = xs.cpu().double(), Cm.cpu().double()
+    D = (torch.cdist(X64, C64) ** 2).min(1).values
+    gm = (d + 2) * U / (1 - (d + 2) * U)
+    E = 2 * gm * (X64.norm(dim=1) + C64.norm(dim=1).max()) ** 2
+    B = E + gm * X64.norm(dim=1) ** 2 + 2 * U * (D + E)
+    valid = bool(((md.cpu().double() - D).abs() <= B + 1e-9 * D).all())  # (1e-9: cdist's own rounding)
+    valid &= abs(float(ph) - float(md.double().sum())) <= 1e-12 * float(ph)
+
+    mind = torch.empty(n, device=dev)
+    near = torch.empty(n, dtype=torch.int32, device=dev)
+    tmind = torch.empty(n, device=dev)
+    blk = 1 << (20 if m <= 1024 else 19)
+
+    def kernel():
+        K.min_dist(X, Cm, mind, near)
+
+    def chain():
+        cn = (Cm * Cm).sum(1)
+        for i in range(0, n, blk):
+            x = X[i:i + blk]
+            d2 = ((x * x).sum(1)[:, None] + cn - 2 * (x @ Cm.T)).min(1).values
+            torch.minimum(tmind[i:i + blk], d2.clamp_(min=0), out=tmind[i:i + blk])
+
+    tk, tt, ta = [], [], []
+    for _ in range(a.steps):  # alternate the three, one timed call each per round, from fresh state
+        for buf, fn, out in ((mind, kernel, tk), (tmind, chain, tt), (None, lambda: K.assign(X, Cm), ta)):
+            for _w in range(a.warmup if not out else 0):
+                fn()
+            if buf is not None:
+                buf.fill_(float("inf"))
+            out += timed(fn, 1, 0)
+    # the full-size result against the chain: either side is within E_i + gamma_{d+2} |x_i|^2 + 2 u dist of the
+    # truth (a dot product of d terms errs by at most gamma_d |x| |c| in any order)
+    xn = torch.cat([(X[i:i + blk] ** 2).sum(1) for i in range(0, n, blk)])
+    tol = 2 * (2 * gm * (xn.sqrt() + float(Cm.norm(dim=1).max())) ** 2 + gm * xn + 2 * U * tmind)
+    agrees = bool(((mind - tmind).abs() <= tol).all())
+    _m, _n, phi = K.min_dist(X, Cm, mind, near)
+    ts = timed(lambda: K.sample(X, mind, phi, float(m), 1, 0), a.steps, a.warmup)
+    picked = len(K.sample(X, mind, phi, float(m), 1, 0)[0])
+
+    rows0 = X[torch.from_numpy(np.random.default_rng(1).choice(n, k, replace=False)).to(dev)].contiguous()
+    t0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0[0].record()
+    seeds, info = K.seed(X, k, seed=1)
+    t0[1].record()
+    t0[1].synchronize()
+    it_r, cost_r = lloyd(X, rows0)
+    it_s, cost_s = lloyd(X, seeds)
+    ms_k, ms_t, ms_a = statistics.median(tk), statistics.median(tt), statistics.median(ta)
+    f_flop, f_byte = 2.0 * n * m * d / PEAK_FLOPS * 1e3, (4.0 * n * d + 12.0 * n) / PEAK_BYTES * 1e3
+    print(json.dumps({"box": box, "op": "seed", "n": n, "d": d, "k": k, "m": m, "valid": bool(valid),
+                      "agrees_with_torch": agrees, "min_dist_ms": round(ms_k, 3), "min_dist_ms_all": [round(t, 3) for t in tk],
+                      "torch_ms": round(ms_t, 3), "torch_over_min_dist": round(ms_t / ms_k, 2),
+                      "assign_ms": round(ms_a, 3), "assign_ms_all": [round(t, 3) for t in ta],
+                      "assign_over_min_dist": round(ms_a / ms_k, 3), "mfma_floor_ms": round(f_flop, 3),
+                      "hbm_floor_ms": round(f_byte, 3), "sample_ms": round(statistics.median(ts), 3),
+                      "sample_ms_all": [round(t, 3) for t in ts], "sample_picked": picked,
+                      "seed_total_ms": round(t0[0].elapsed_time(t0[1]), 1), "seed_candidates": len(info["candidates"]),
+                      "lloyd_rows": {"iters": it_r, "cost": cost_r}, "lloyd_kmeans||": {"iters": it_s, "cost": cost_s}}),
+          flush=True)
+    return 0 if valid and agrees else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 24)
@@ -136,6 +227,7 @@ def main():
     ap.add_argument("--shapes", default=",".join(f"{d}x{k}" for d in (16, 64, 128) for k in (16, 256, 1024)))
     ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--terms", type=int, default=3)
+    ap.add_argument("--op", choices=("step", "seed"), default="step")
     a = ap.parse_args()
     if a.dtype == "fp32" and a.terms != 3:
         ap.error("--terms goes with --dtype bf16")
@@ -147,6 +239,10 @@ def main():
     for shape in a.shapes.split(","):
         d, k = (int(v) for v in shape.split("x"))
         X, C = make(a.n, d, k, dev)
+        if a.op == "seed":
+            bad += bench_seed(a, X, box, d, k)
+            del X, C
+            continue
         if a.dtype == "bf16":
             bad += bench_bf16(a, X.to(torch.bfloat16), X, C, box)
             del X, C

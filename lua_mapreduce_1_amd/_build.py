@@ -34,10 +34,11 @@ HIP_LIB = os.path.join(LIBDIR, "libmrhip.so")
 COORD_LIB = os.path.join(LIBDIR, "libmrcoord.so")
 HOST_LIB = os.path.join(LIBDIR, "libmrhost.so")
 
-# per-file compiler flags: the k-means kernels' fp32 error bounds assume scalar
+# per-file compiler flags: the k-means and mixture kernels' fp32 error bounds assume scalar
 # (unpacked) fp32 arithmetic around their MFMA chains
 _UNPACKED = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-HIP_EXTRA = {"kmeans.hip": _UNPACKED, "kmeans_bf16.hip": _UNPACKED, "kmeans_seed.hip": _UNPACKED}
+HIP_EXTRA = {"kmeans.hip": _UNPACKED, "kmeans_bf16.hip": _UNPACKED, "kmeans_seed.hip": _UNPACKED,
+             "gmm.hip": _UNPACKED}
 
 
 def _newer(target: str, sources: list[str]) -> bool:

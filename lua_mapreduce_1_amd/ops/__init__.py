@@ -5,3 +5,4 @@ from .primitives import (HashTable, tokenize, key_meta, key_bytes_list, exclusiv
                          exact_key_perm, gather_aos4)
 from . import keys  # noqa: F401
 from . import kmeans  # noqa: F401
+from . import gmm  # noqa: F401

@@ -74,6 +74,10 @@ _SIGS = {
                                _p],
     "mr_kmeans_sample_write": [_p, _i32, _p, ctypes.c_longlong, _i32, _u64, ctypes.c_double, ctypes.c_double, _u32,
                                _u32, _p, _p, _p, _p],
+    "mr_gmm_run": [],
+    "mr_gmm_prepare": [_p, _p, _p, _i32, _i32, _p, _p, _p],
+    "mr_gmm_score": [_p, _p, _p, ctypes.c_longlong, _i32, _i32, _p, _p, _p, _p],
+    "mr_gmm_stats": [_p, _p, _p, _p, ctypes.c_longlong, _i32, _i32, _p, _p, _p, _p],
     "mr_count_newlines": [_p, _u64, _u64, _p, _p, _p],
     "mr_ii_map": [_p, _u64, _u64, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _u64, _u32, _p, _p, _u64, _p, _p],
     "mr_ii_advance": [_p, _p, _p],

@@ -6,3 +6,4 @@ from .primitives import (HashTable, tokenize, key_meta, key_bytes_list, exclusiv
 from . import keys  # noqa: F401
 from . import kmeans  # noqa: F401
 from . import gmm  # noqa: F401
+from . import knn  # noqa: F401

@@ -7,3 +7,4 @@ from . import keys  # noqa: F401
 from . import kmeans  # noqa: F401
 from . import gmm  # noqa: F401
 from . import knn  # noqa: F401
+from . import gram  # noqa: F401

@@ -38,7 +38,8 @@ HOST_LIB = os.path.join(LIBDIR, "libmrhost.so")
 # (unpacked) fp32 arithmetic around their MFMA chains
 _UNPACKED = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_EXTRA = {"kmeans.hip": _UNPACKED, "kmeans_bf16.hip": _UNPACKED, "kmeans_seed.hip": _UNPACKED,
-             "gmm.hip": _UNPACKED, "knn.hip": _UNPACKED, "gram.hip": _UNPACKED}
+             "gmm.hip": _UNPACKED, "knn.hip": _UNPACKED, "gram.hip": _UNPACKED,
+             "glm.hip": _UNPACKED}
 
 
 def _newer(target: str, sources: list[str]) -> bool:

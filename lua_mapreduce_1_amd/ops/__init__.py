@@ -8,3 +8,4 @@ from . import kmeans  # noqa: F401
 from . import gmm  # noqa: F401
 from . import knn  # noqa: F401
 from . import gram  # noqa: F401
+from . import glm  # noqa: F401

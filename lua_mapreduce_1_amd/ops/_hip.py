@@ -85,6 +85,9 @@ _SIGS = {
     "mr_gram_run": [],
     "mr_gram_workspace_bytes": [_i32, _i32],
     "mr_gram_moments": [_p, _p, _p, ctypes.c_longlong, _i32, _i32, _i32, _p, _p, _p, _p],
+    "mr_glm_run": [],
+    "mr_glm_workspace_bytes": [_i32, _i32],
+    "mr_glm_newton": [_p, _p, _p, ctypes.c_longlong, _i32, _i32, _p, _p, _p, _p, _p],
     "mr_count_newlines": [_p, _u64, _u64, _p, _p, _p],
     "mr_ii_map": [_p, _u64, _u64, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _u64, _u32, _p, _p, _u64, _p, _p],
     "mr_ii_advance": [_p, _p, _p],
@@ -186,7 +189,7 @@ _SIGS = {
     "mr_unpack_splits": [_p, _u64, _p, _u64, _p, _u64, _u64, _p, _u64, _p],
     "mr_undict_splits": [_p, _u64, _p, _u64, _p, _u64, _u64, _p, _u64, _p, _u64, _p],
 }
-_RESTYPE_U64 = {"mr_gram_workspace_bytes", "mr_knn_workspace_bytes","mr_compact_pack_ws_bytes", "mr_ii_unique_tiles", "mr_text_tiles", "mr_scan_partials_len", "mr_tail_pack_bytes", "mr_tail_ws_layout",
+_RESTYPE_U64 = {"mr_gram_workspace_bytes", "mr_glm_workspace_bytes", "mr_knn_workspace_bytes","mr_compact_pack_ws_bytes", "mr_ii_unique_tiles", "mr_text_tiles", "mr_scan_partials_len", "mr_tail_pack_bytes", "mr_tail_ws_layout",
                 "mr_tail_bhist_bytes", "mr_onesweep_tiles", "mr_rec_tie_ws_words", "mr_sdma_d2h_begin",
                 "mr_gather_copy_chunk", "mr_mrc1_encode_unit", "mr_mrc1_encode_units", "mr_mrc2_encode_unit", "mr_mrl1_encode_unit"}
 
